@@ -13,16 +13,23 @@ reference's jobs: 10 warm-up + 20 timed iterations (jobs/bwunicluster/pencil/ben
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8        # ... or runs inside ranks somebody else started
     python bench.py --dry-run            # build the C4 / C5 plans of all 8 ranks on a host without a GPU
+    python bench.py --full               # the headline plus every other leg and check listed below
+    python bench.py --dump-outputs DIR   # also write samples of the last timed step's outputs (DIR/spectrum.npy, DIR/round_trip.npy)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+A plain run sets up, tunes the plan's kernel configurations, warms up, times --steps steps and prints the line.  Everything
+else -- the round-trip check at N = 1, the legs that take runs of their own and the CPU baseline -- runs with --full only.
+
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) with extra objects:
   roofline          -- achieved HBM GB/s of the dominant kernel (the axis-pass kernel), from algorithmic bytes per
-                       launch / HIP-event duration on the launch stream
-  cpu_baseline      -- the CPU oracle (a port: the reference has no CPU path) timed on this host
+                       launch / HIP-event duration on the launch stream (the timed steps themselves)
+  round_trip_rel_linf (--full, and always at N > 1) -- max |back / N^3 - x| / max |x| after the warm-up
+  config.plain_buffers (--full, N = 1) -- the same plan on the caller's plain allocator, and an unmodified caller's buffers
+  cpu_baseline (--full) -- the CPU oracle (a port: the reference has no CPU path) timed on this host
   config.per_pass   -- device time and achieved TB/s of every pass of the timed plan
-  config.multi_rank_path (N = 1 only) -- the same grid through the code path every rank runs at N > 1: mirrored
+  config.multi_rank_path (--full, N = 1) -- the same grid through the code path every rank runs at N > 1: mirrored
                        inverse order (x, y, z) and segmented (8-chunk) address tables, so that a 1-GPU lease
                        predicts the per-GPU compute of the multi-GPU runs
-  config.per_gpu_kernels_8gpu (N = 1 only) -- rank 0's plan of the 8-GPU decompositions (pencil 2x4 = BASELINE C4, slab 8)
+  config.per_gpu_kernels_8gpu (--full, N = 1) -- rank 0's plan of the 8-GPU decompositions (pencil 2x4 = BASELINE C4, slab 8)
                        executed on this GPU with the exchange stubbed out: the kernels one GPU of the 8-GPU run launches
                        (its 1/8 of the volume, its segment tables and pipeline chunks), timed with HIP events.  Both legs
                        call the plan's own tuner first (dfft_tune_variants, as bench.py does at N > 1; `tune_variants`
@@ -32,7 +39,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
 
 At N > 1 the headline decomposition is the one BASELINE.json names (8 GPUs: pencil 2x4, 4: pencil 2x2, 2: slab); the slab
 decomposition over all N ranks -- one exchange over N-1 private xGMI links instead of two over 3 + 1 -- is measured in the
-same run and reported as config.alt (--decomp slab makes it the headline).
+same run with --full and reported as config.alt (--decomp slab makes it the headline).
 """
 import argparse
 import json
@@ -92,6 +99,15 @@ def parse():
     ap.add_argument("--pmc", type=int, default=0,
                     help="1 (N = 1, the default workload): measure roofline.traffic in this run -- two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE, "
                          "kernel trace only) over tools/kbench on the same grid, after the timed region -- instead of carrying the committed figure")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check besides the headline: the round-trip check after the warm-up (N = 1), "
+                         "the plain-buffer and unmodified-caller legs, the multi-rank code path, the per-GPU kernels of the 8-GPU plans, "
+                         "the alternative decomposition and the CPU baseline (the --no-* options still switch single legs off).  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: spectrum (the forward "
+                         "output) and round_trip (the inverse output), each a fixed seeded sample of at most 2^20 entries, "
+                         "[k, 2] (re, im) in the run's precision; ranks > 0 of a multi-rank run add _rank<r> to the name")
     ap.add_argument("--dry-run", action="store_true", help="plan C4 / C5 for all 8 ranks without a GPU and print the memory budget")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="launcher check (no GPU needed): the ranks meet over gloo, rank 0 prints the world it saw, everybody leaves")
@@ -137,6 +153,38 @@ def xgmi_model(esz, N, ngpus, P1, P2):
 
 def flops_per_direction(n):
     return 5.0 * float(n) ** 3 * math.log2(float(n) ** 3)
+
+
+DUMP_SAMPLE = 1 << 20      # entries per dumped array: 2 x 2^20 fp64 complex = 32 MiB per rank
+DUMP_SEED = 20261016
+
+
+def dump_positions(out_size, out_strides, n_in):
+    """--dump-outputs: element offsets of the entries that are written out -- of the spectrum (forward output: this rank's
+    (Nx, yo, zs) block, whatever the plan's spectral layout) and of the inverse output (this rank's input block).  Blocks larger
+    than DUMP_SAMPLE entries are sampled at DUMP_SEED's sorted positions (row-major over the block): the same positions in every
+    run with the same arguments."""
+    import numpy as np
+
+    def positions(n):
+        if n <= DUMP_SAMPLE:
+            return np.arange(n, dtype=np.int64)
+        return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False)).astype(np.int64)
+
+    i = positions(out_size[0] * out_size[1] * out_size[2])
+    k0, rest = np.divmod(i, out_size[1] * out_size[2])
+    k1, k2 = np.divmod(rest, out_size[2])
+    return k0 * out_strides[0] + k1 * out_strides[1] + k2 * out_strides[2], positions(n_in)
+
+
+def write_dump(dirname, rank, world, arrays):
+    """arrays: {name: complex device tensor} -> dirname/<name>.npy as [k, 2] (re, im) of the run's real type"""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 and rank > 0 else ""
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + suffix + ".npy"), np.ascontiguousarray(torch.view_as_real(t).cpu().numpy()))
 
 
 def cpu_baseline(n_req):
@@ -540,7 +588,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run_steps(pl, k, out_buf, back_buf, collect=False):
+    def run_steps(pl, k, out_buf, back_buf, collect=False, capture=None):
         """k forward + inverse pairs; returns (seconds, {phase name: total ms}, launches of FFT passes).
         Normally ONE bracket (barrier + synchronize on both sides) around all k steps.  When the inverse writes back over
         the input (`aliased`: 2048^3 fp32 on one GPU) every step multiplies the data by N^3, which overflows fp32 within
@@ -559,6 +607,8 @@ def main():
             with torch.cuda.stream(side):
                 pl.execC2C(out_buf, d_in, dfft.FORWARD)       # blocking, like the reference's exec
                 ph_f = pl.getPhaseTimes(dfft.FORWARD) if collect else []
+                if capture is not None and i == k - 1:
+                    capture(out_buf)      # --dump-outputs: the spectrum of the last step, before the inverse uses it as scratch
                 pl.execC2C(back_buf, out_buf, dfft.INVERSE)
                 ph_b = pl.getPhaseTimes(dfft.INVERSE) if collect else []
             for name, ms in ph_f + ph_b:
@@ -583,7 +633,8 @@ def main():
 
     def warm_and_check(pl, out_buf, back_buf):
         run_steps(pl, args.warmup, out_buf, back_buf)
-        if args.warmup == 0:
+        # N > 1 always checks: a wrong native RCCL round trip switches the headline to the torch transport (below)
+        if args.warmup == 0 or not (args.full or world > 1):
             return None
         return round_trip_error(back_buf)      # round-trip check on the warm-up result (reference testcase 3), worst rank
 
@@ -606,8 +657,22 @@ def main():
     if aliased:
         fill(d_in)          # the timed region must start from the input, not from a round-tripped copy
 
+    capture, dumped = None, {}
+    if args.dump_outputs:
+        # the inverse destroys its input (include/dfft_c.h): the spectrum is gathered on the plan's stream right after the last
+        # timed forward (2^20 entries at most), the inverse output after the last step
+        spec_off, back_off = dump_positions(plan.getOutSize(), plan.getOutStrides(), n_in)
+        assert spec_off.max() < d_out.numel() and back_off.max() < d_back.numel(), "dump positions outside the buffers"
+        spec_off, back_off = torch.from_numpy(spec_off).cuda(), torch.from_numpy(back_off).cuda()
+
+        def capture(out_buf):
+            dumped["spectrum"] = out_buf.reshape(-1)[spec_off]
+
     plan.enablePhaseTiming(True)
-    dt, phases, kern_launches = run_steps(plan, args.steps, d_out, d_back, collect=True)
+    dt, phases, kern_launches = run_steps(plan, args.steps, d_out, d_back, collect=True, capture=capture)
+    if args.dump_outputs:
+        dumped["round_trip"] = d_back.reshape(-1)[back_off]
+        write_dump(args.dump_outputs, rank, world, dumped)
     kern_ms = sum(ms for name, ms in phases.items() if "FFT" in name)
     exch_ms = sum(ms for name, ms in phases.items() if "FFT" not in name)
 
@@ -830,7 +895,7 @@ def main():
     # cudaMalloc'd in / out, tests/src/pencil/random_dist_3D.cu:197-205) and a hipMalloc work area, no tuner of any kind
     plain_leg = None
     free_b, _ = torch.cuda.mem_get_info()
-    if ngpus == 1 and not args.no_plain_leg and not args.plain_buffers and not aliased and free_b > 3 * domain + n_in * esz + (4 << 30):
+    if args.full and ngpus == 1 and not args.no_plain_leg and not args.plain_buffers and not aliased and free_b > 3 * domain + n_in * esz + (4 << 30):
         pp = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), None, precision=prec, rank=0)
         pp.initFFT(dfft.GlobalSize(N, N, N), dfft.Partition(1, 1), allocate=False, c2c=True)
         pp.setStream(stream)
@@ -946,10 +1011,10 @@ def main():
     # N = 1: the code path of the N > 1 runs on the same grid (mirrored inverse order, 8-chunk segment tables)
     multi_rank_path = None
     free_b, _ = torch.cuda.mem_get_info()
-    if ngpus == 1 and not args.no_multi_rank_path and free_b < plan.getWorkSizeDevice() + (2 << 30):
+    if args.full and ngpus == 1 and not args.no_multi_rank_path and free_b < plan.getWorkSizeDevice() + (2 << 30):
         del plan            # 2048^3 fp32: only one work area fits next to the grid
         plan = None
-    if ngpus == 1 and not args.no_multi_rank_path:
+    if args.full and ngpus == 1 and not args.no_multi_rank_path:
         plan_m, _, _, _ = make_plan(1, 1, {"mirror_inverse": 1, "pipeline_chunks": 8})
         ksteps = max(1, min(args.steps, 10))
         tuned_m = None
@@ -977,7 +1042,7 @@ def main():
 
     # N = 1: the kernels one GPU of the 8-GPU runs launches (BASELINE C4 / C5 grids: pencil 2x4; and slab 8), exchange stubbed
     per_gpu_8 = None
-    if ngpus == 1 and not args.no_multi_rank_path and N % 8 == 0:
+    if args.full and ngpus == 1 and not args.no_multi_rank_path and N % 8 == 0:
         fill(d_in)
         per_gpu_8 = [per_gpu_kernels(2, 4, 5), per_gpu_kernels(8, 1, 5)]
         # the same plans with the spectrum kept x-contiguous (option spectral_layout = 1: neither x pass touches the point-major layout)
@@ -991,7 +1056,7 @@ def main():
     # the other decomposition (slab over all ranks next to the BASELINE pencil grid, or the reverse) in the same run
     alt = None
     alt_part = (ngpus, 1) if P2 > 1 else pencil_partition(ngpus)
-    if world > 1 and not args.no_alt and alt_part != (P1, P2) and not (args.p1 and args.p2):
+    if args.full and world > 1 and not args.no_alt and alt_part != (P1, P2) and not (args.p1 and args.p2):
         if not aliased:
             del d_back
         plan2, comm2, transport2, work2 = make_plan(*alt_part)
@@ -1070,7 +1135,7 @@ def main():
             xg["predicted_exchange_ms_per_step"] = round(2.0 * sum(m["predicted_ms"] for m in model.values()), 3)
             out["xgmi"] = xg
             out["overlap"] = overlap_report(ms_per_step, kern_ms / args.steps, exch_ms / args.steps)
-        if not args.no_cpu_baseline and ngpus == 1:
+        if args.full and not args.no_cpu_baseline and ngpus == 1:
             out["cpu_baseline"] = cpu_baseline(args.cpu_n)
         print(json.dumps(out), flush=True)
     if dist is not None:

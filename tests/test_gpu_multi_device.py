@@ -75,7 +75,7 @@ def test_one_process_per_gpu_against_the_oracle(kind, grid, transport):
 def test_bench_runs_on_all_gpus():
     nproc = 2 if NDEV < 4 else (4 if NDEV < 8 else 8)
     # exactly the driver's command line: bench.py starts its own ranks
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--size", "256", "--steps", "3", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--size", "256", "--steps", "3", "--warmup", "1", "--full"]
     env = dict(os.environ, PYTHONPATH=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)

@@ -605,7 +605,7 @@ def test_bench_multi_rank_line_is_self_documenting(nproc, want, alt):
     next to the measured exchange spans) and overlap.hidden_frac"""
     # (pencil grids: the relayed run is made the headline whatever its time, to exercise that branch: on ranks that share one GPU
     # over gloo it is never the faster one.  The 4-rank case -- launched under torch.distributed.run -- is behind the `slow` marker.)
-    line = _bench(["--gpus", str(nproc), "--backend", "gloo", "--size", "128", "--steps", "2", "--warmup", "1"] + (["--prefer-relay"] if nproc >= 4 else []),
+    line = _bench(["--gpus", str(nproc), "--backend", "gloo", "--size", "128", "--steps", "2", "--warmup", "1", "--full"] + (["--prefer-relay"] if nproc >= 4 else []),
                   nproc=nproc, port=29671 + nproc, self_launch=nproc != 4)      # 2 and 8 ranks: bench.py launches them itself
     assert line["n_gpus"] == nproc and line["round_trip_rel_linf"] < 1e-10
     assert line["config"]["decomposition"] == want
@@ -636,7 +636,7 @@ def test_bench_multi_rank_line_is_self_documenting(nproc, want, alt):
 
 def test_bench_single_gpu_line_carries_the_8gpu_kernels():
     """N = 1: roofline object, the multi-rank code path and the per-GPU kernels of the 8-GPU plans (exchange stubbed)"""
-    line = _bench(["--size", "256", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    line = _bench(["--size", "256", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert line["n_gpus"] == 1 and line["round_trip_rel_linf"] < 1e-10 and line["roofline"]["bound"] == "hbm"
     plans = line["config"]["per_gpu_kernels_8gpu"]["plans"]
     assert [p["decomposition"] for p in plans] == ["pencil 2x4", "slab P=8"]
@@ -645,3 +645,29 @@ def test_bench_single_gpu_line_carries_the_8gpu_kernels():
         assert p["alg_bytes_per_pass"] == 2 * 16 * 256 ** 3 / 8
     assert set(plans[0]["xgmi_model_per_transform"]) == {"exchange 1", "exchange 2"}
     assert set(plans[1]["xgmi_model_per_transform"]) == {"exchange 2"}
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run (no --full) carries the headline of --steps timed steps and none of the other legs; --dump-outputs writes what
+    the last timed step computed from the same input in every run: two runs agree, and the inverse output is N^3 times the
+    inverse transform of the spectrum"""
+    n = 64
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        lines.append(_bench(["--size", str(n), "--steps", "4", "--warmup", "1", "--dump-outputs", str(d)]))
+        dumps.append({name: np.load(d / f"{name}.npy") for name in ("spectrum", "round_trip")})
+    line = lines[0]
+    assert line["n_gpus"] == 1 and line["steps"] == 4 and line["unit"] == "GFLOP/s" and line["higher_is_better"] and line["dtype"] == "f64"
+    flops_step = 2 * 5.0 * n ** 3 * math.log2(n ** 3)
+    assert line["ms_per_step"] > 0 and abs(line["value"] - flops_step / (line["ms_per_step"] * 1e-3) / 1e9) <= 0.05 * line["value"]
+    assert not {"plain_buffers", "multi_rank_path", "per_gpu_kernels_8gpu", "alt"} & set(line["config"]) and "cpu_baseline" not in line
+    spec, back = dumps[0]["spectrum"], dumps[0]["round_trip"]
+    assert spec.shape == back.shape == (n ** 3, 2) and spec.dtype == back.dtype == np.float64
+    spec_c = (spec[:, 0] + 1j * spec[:, 1]).reshape(n, n, n)
+    back_c = (back[:, 0] + 1j * back[:, 1]).reshape(n, n, n)
+    assert np.max(np.abs(np.fft.ifftn(spec_c) * n ** 3 - back_c)) < 1e-12 * np.max(np.abs(back_c))
+    assert -1e-6 < back_c.real.min() / n ** 3 and back_c.real.max() / n ** 3 < 255.0 + 1e-6        # the input is uniform on [0, 255)
+    for name in ("spectrum", "round_trip"):
+        a, b = dumps[0][name], dumps[1][name]
+        assert np.max(np.abs(a - b)) < 1e-12 * np.max(np.abs(a)), name

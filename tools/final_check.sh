@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/final_check.sh [TAG] -- the end-of-session check in ONE gpurun call (about 15 GPU-minutes):
 #   gpurun --timeout 2400 -- 'bash tools/final_check.sh r4'
-# full GPU parity suite, the default bench line, the same line under rocprofv3 --kernel-trace --stats, and the PMC traffic of the
+# full GPU parity suite, the bench line with every leg (--full), the same line under rocprofv3 --kernel-trace --stats, and the PMC traffic of the
 # library as it is (FETCH_SIZE / WRITE_SIZE in separate passes; the json records the library's sha256, bench.py refuses another's).
 TAG=${1:-r6}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -40,8 +40,8 @@ else
   timeout 900 python -m pytest tests -x -q -m gpu -k "$SUITE" --durations=10 > $OUT/${TAG}_pytest_gpu_subset.txt 2>&1; tail -14 $OUT/${TAG}_pytest_gpu_subset.txt
 fi
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-T0=$(date +%s); timeout 500 python bench.py > $OUT/bench_${TAG}.json 2> $OUT/bench.err; echo "bench.py (default flags) took $(( $(date +%s) - T0 )) s"; tail -c 400 $OUT/bench_${TAG}.json; echo; tail -3 $OUT/bench.err
-timeout 300 python bench.py --size 2048 --precision float --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_${TAG}_f32_2048.json 2> $OUT/bench_f32_2048.err; tail -c 300 $OUT/bench_${TAG}_f32_2048.json; echo
+T0=$(date +%s); timeout 500 python bench.py --full > $OUT/bench_${TAG}.json 2> $OUT/bench.err; echo "bench.py --full took $(( $(date +%s) - T0 )) s"; tail -c 400 $OUT/bench_${TAG}.json; echo; tail -3 $OUT/bench.err
+timeout 300 python bench.py --size 2048 --precision float --steps 5 --warmup 2 --full --no-cpu-baseline > $OUT/bench_${TAG}_f32_2048.json 2> $OUT/bench_f32_2048.err; tail -c 300 $OUT/bench_${TAG}_f32_2048.json; echo
 ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -o bench -- python $R/bench.py --no-cpu-baseline --no-multi-rank-path --no-plain-leg > $OUT/bench_${TAG}_profiled.json 2> $OUT/prof_bench.log )
 find $OUT/prof_bench -name "*kernel_stats.csv" -exec cp {} $OUT/${TAG}_bench_kernel_stats.csv \;
 find $OUT/prof_bench -name "*kernel_trace.csv" -exec cp {} $OUT/${TAG}_bench_kernel_trace.csv \;

@@ -47,18 +47,18 @@ COUNTS="2 4 8"
 for g in $COUNTS; do
     [ "$g" -gt "$N" ] && [ "${DRY:-0}" != 1 ] && continue
     for tr in rccl torch; do
-        run ${TAG}_bench_${g}gpu_${tr} $T_BENCH python bench.py --gpus "$g" --steps "$STEPS" --warmup "$WARM" --transport $tr --no-cpu-baseline
+        run ${TAG}_bench_${g}gpu_${tr} $T_BENCH python bench.py --gpus "$g" --steps "$STEPS" --warmup "$WARM" --transport $tr --full --no-cpu-baseline
     done
 done
 if [ "${DRY:-0}" = 1 ]; then
     # the 8-rank world on ONE GPU: gloo ranks sharing the device (no RCCL: it refuses two ranks per device), small grid
-    run ${TAG}_bench_8ranks_gloo_1gpu $T_BENCH python bench.py --gpus 8 --backend gloo --transport torch --size 256 --steps 3 --warmup 1 --no-cpu-baseline
+    run ${TAG}_bench_8ranks_gloo_1gpu $T_BENCH python bench.py --gpus 8 --backend gloo --transport torch --size 256 --steps 3 --warmup 1 --full --no-cpu-baseline
 fi
 
 # 3. kernel trace of the largest run (rank 0 of the self-launched world is the profiled process' child: trace the launcher tree)
 G=$N; [ "${DRY:-0}" = 1 ] && G=1
 ( cd /tmp && timeout "$T_PROF" rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_${G}gpu" -o bench -- \
-    python "$R/bench.py" --gpus "$G" --steps 5 --warmup 2 --transport rccl --no-cpu-baseline --relay 0 --no-multi-rank-path --no-plain-leg \
+    python "$R/bench.py" --gpus "$G" --steps 5 --warmup 2 --transport rccl --full --no-cpu-baseline --relay 0 --no-multi-rank-path --no-plain-leg \
     > "$OUT/${TAG}_bench_${G}gpu_profiled.json" 2> "$OUT/${TAG}_bench_${G}gpu_profiled.err" )
 log "profiled run: exit $?"
 find "$OUT/prof_${G}gpu" -name "*kernel_stats.csv" | head -8 | while read -r f; do cp "$f" "$OUT/${TAG}_${G}gpu_$(basename "$(dirname "$f")")_kernel_stats.csv"; done

@@ -12,7 +12,7 @@ cd $R
 K=$R/tools/kbench
 export TMPDIR=/tmp
 timeout 1200 python -m pytest tests -x -q -m gpu --durations=10 > $OUT/pytest_gpu.txt 2>&1; tail -14 $OUT/pytest_gpu.txt
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.json; echo
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.json; echo
 # five more bench lines from fresh processes (placement tuner on, its default) and two with plain allocations
 for i in 1 2 3 4 5; do python bench.py --no-cpu-baseline --no-multi-rank-path > $OUT/bench_fresh_$i.json 2>> $OUT/bench.err; done
 for i in 1 2; do python bench.py --no-cpu-baseline --no-multi-rank-path --tune-placement 0 > $OUT/bench_plain_$i.json 2>> $OUT/bench.err; done
@@ -36,7 +36,7 @@ prof() {  # name, command...: rocprofv3 kernel trace + stats of a command, stats
 }
 # every axis-pass launch of this command is one full pass (the multi-rank leg, whose launches are 1/8 passes, is profiled separately below)
 prof bench python $R/bench.py --no-cpu-baseline --no-multi-rank-path
-python bench.py --size 2048 --precision float --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_f32_2048.json 2> $OUT/bench_f32_2048.err; tail -c 300 $OUT/bench_f32_2048.json; echo
+python bench.py --size 2048 --precision float --steps 5 --warmup 2 --full --no-cpu-baseline > $OUT/bench_f32_2048.json 2> $OUT/bench_f32_2048.err; tail -c 300 $OUT/bench_f32_2048.json; echo
 prof f32_2048 $K --size 2048 --prec f32 --iters 3
 prof f32_2048_multirank $K --size 2048 --prec f32 --iters 3 --opt mirror_inverse=1 --opt pipeline_chunks=8
 prof f64_2048z $K --size 1024x1024x2048 --prec f64 --iters 3
