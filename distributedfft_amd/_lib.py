@@ -34,6 +34,11 @@ class PassDesc(C.Structure):
                 ("sstart", C.c_uint32 * 32), ("slen", C.c_uint32 * 32), ("sbase", C.c_uint64 * 32)]
 
 
+class ChainStep(C.Structure):
+    _fields_ = [("group", C.c_char * 8), ("axis", C.c_int32), ("launches", C.c_int32), ("per_chunk", C.c_int32),
+                ("src", C.c_int32), ("dst", C.c_int32), ("conj", C.c_int32), ("form", C.c_int32), ("exchange", C.c_int32)]
+
+
 # every symbol include/dfft_c.h declares: (name, restype, argtypes)
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 _psz = C.POINTER(C.c_size_t)
@@ -86,6 +91,7 @@ SYMBOLS = [
     ("dfft_fft1d_batched_ex", _i, [_i, _sz, _sz, _vp, _vp, _i, _vp, _i, _i]),
     ("dfft_get_pass_choices", _i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     ("dfft_debug_get_pass", _i, [_vp, C.c_char_p, _i, C.POINTER(PassDesc)]),
+    ("dfft_debug_get_chain", _i, [_vp, _i, _i, C.POINTER(ChainStep), _i, C.POINTER(_i)]),
     ("dfft_debug_get_point_table", _i, [_vp, C.c_char_p, _i, _i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint32), _sz, _psz]),
     ("dfft_last_error", C.c_char_p, []),

@@ -468,6 +468,15 @@ class MPIcuFFT:
             return None
         return d
 
+    def debugChain(self, direction, dims=3):
+        """the steps of the chain the next exec would run (dfft_debug_get_chain): one dict per step, keys as dfft_chain_step"""
+        from ._lib import ChainStep
+        n = C.c_int(0)
+        check(lib().dfft_debug_get_chain(self._h, int(direction), int(dims), None, 0, C.byref(n)))
+        steps = (ChainStep * n.value)()
+        check(lib().dfft_debug_get_chain(self._h, int(direction), int(dims), steps, n.value, C.byref(n)))
+        return [{k: (getattr(s, k).decode() if k == "group" else getattr(s, k)) for k, _ in ChainStep._fields_} for s in steps]
+
     def debugPointTable(self, name, index=0, store=False):
         """[(base, ln, aux)] per point of a segmented side (dfft_debug_get_point_table)"""
         n = C.c_size_t(0)

@@ -340,67 +340,43 @@ static int launch_long_bluestein(int prec, const Axis &ax, const PassArgs &P, in
     return 0;
 }
 
-// complex axis pass on axis `axis` (0 = z, 1 = y, 2 = x)
-static int launch(dfft_plan *p, const Launch &L, int variant, int axis, const char *in, char *out, bool real_lines = false, hipStream_t stream = nullptr)
+// the launches of one group on axis `axis` (0 = z, 1 = y, 2 = x) in line form `form` (LineForm); conj: with conjugation
+static int launch(dfft_plan *p, const Launch &L, int form, int axis, bool conj, const char *in, char *out, hipStream_t stream)
 {
     if (L.args.ntiles == 0) return 0;
-    if (!stream) stream = p->stream;
     const Axis &ax = p->ax[axis];
     PassArgs A = L.args;
     A.in = in + L.in_off; A.out = out + L.out_off; A.tw = ax.tw; A.debug = p->opt.debug;
+    if (conj) A.swap = 1;
     fill_tables(p, L, A);
-    if (real_lines && p->yreal_native && axis == 1) {      // packed real kernel on strided lines (Y_Then_ZX)
+    // real forms: real lines in / out (real_mode 1 R2C, 2 C2R), the Hermitian half of NK = N/2 + 1 points on the other side
+    const int real_mode = form == FORM_REAL_Z1 || form == FORM_REAL_LINES ? 1 : form == FORM_REAL_Z2 ? 2 : 0;
+    const size_t NK = real_mode ? ax.N / 2 + 1 : ax.N;
+    if (real_mode && (form == FORM_REAL_LINES ? p->yreal_native : p->zreal_native)) {
+        // packed kernels: N/2-point complex transform + split / merge; the z pass of an R2C plan (A/B configurations: real_variant),
+        // the strided real lines of a Y_Then_ZX R2C plan
         A.tw2 = p->tw_zr;
-        const int M = (int)(p->Ny / 2);
-        const int r = p->prec == DFFT_F64 ? launch_real_f64(M, 1, 0, A, stream) : launch_real_f32(M, 1, 0, A, stream);
-        if (r != 0) return fail(r == -1 ? ERR_UNSUPPORTED : r, "real y pass launch failed for length " + std::to_string(p->Ny));
+        const bool z = form != FORM_REAL_LINES;
+        const int M = (int)((z ? p->Nz : p->Ny) / 2), variant = z ? p->opt.real_variant : 0;
+        const int r = p->prec == DFFT_F64 ? launch_real_f64(M, real_mode, variant, A, stream) : launch_real_f32(M, real_mode, variant, A, stream);
+        if (r != 0) return fail(r == -1 ? ERR_UNSUPPORTED : r, "real pass launch failed for length " + std::to_string(2 * M));
         return 0;
     }
-    if (!ax.bluestein) return launch_pass(p->prec, (int)ax.N, variant, A, stream);
+    if (!ax.bluestein) {
+        if (real_mode) return fail(ERR_UNSUPPORTED, "real pass without a packed or Bluestein plan");      // (dfft_init rules this out)
+        return launch_pass(p->prec, (int)ax.N, form == FORM_FWD ? p->vfwd[axis] : form == FORM_INV ? p->vinv[axis] : 0, A, stream);
+    }
     if (ax.longb) {
         if (long_bytes(A, p->TL, ax.M, p->esz) > p->lv_bytes) return fail(ERR_STATE, "long Bluestein pass: scratch region too small");
-        return launch_long_bluestein(p->prec, ax, A, real_lines ? 1 : 0, real_lines ? ax.N / 2 + 1 : ax.N, static_cast<char *>(p->work_d) + p->lv_off, p->TL, stream);
+        return launch_long_bluestein(p->prec, ax, A, real_mode, NK, static_cast<char *>(p->work_d) + p->lv_off, p->TL, stream);
     }
     if (ax.two) {
         if (two_level_bytes(A, p->TL, ax.N, p->esz) > p->lv_bytes) return fail(ERR_STATE, "two-level pass: scratch region too small");
-        return launch_two_level(p->prec, ax, A, real_lines ? 1 : 0, real_lines ? ax.N / 2 + 1 : ax.N, static_cast<char *>(p->work_d) + p->lv_off, p->TL, stream);
+        return launch_two_level(p->prec, ax, A, real_mode, NK, static_cast<char *>(p->work_d) + p->lv_off, p->TL, stream);
     }
-    A.NK = (uint32_t)ax.N; A.real_mode = 0;
-    if (real_lines) { A.real_mode = 1; A.NK = (uint32_t)(ax.N / 2 + 1); }     // real in, Hermitian half out
-    int r = launch_generic(p->prec, ax, A, stream);
+    A.NK = (uint32_t)NK; A.real_mode = real_mode;
+    const int r = launch_generic(p->prec, ax, A, stream);
     if (r != 0) return fail(r == -1 ? ERR_UNSUPPORTED : r, "Bluestein pass launch failed for length " + std::to_string(ax.N));
-    return 0;
-}
-
-// z pass of an R2C plan.  Power-of-two Nz: M = Nz/2 point complex FFT + split (mode 1) / merge
-// (mode 2); any other Nz: Bluestein on the real line (real_mode 1 / 2).
-static int launch_real(dfft_plan *p, const Launch &L, int mode, const char *in, char *out, hipStream_t stream = nullptr)
-{
-    if (L.args.ntiles == 0) return 0;
-    if (!stream) stream = p->stream;
-    const Axis &ax = p->ax[0];
-    PassArgs A = L.args;
-    A.in = in + L.in_off; A.out = out + L.out_off; A.tw = ax.tw; A.tw2 = p->tw_zr; A.debug = p->opt.debug;
-    fill_tables(p, L, A);
-    int r;
-    if (p->zreal_native) {
-        const int M = (int)(p->Nz / 2);
-        r = p->prec == DFFT_F64 ? launch_real_f64(M, mode, p->opt.real_variant, A, stream)
-                                : launch_real_f32(M, mode, p->opt.real_variant, A, stream);
-    } else if (!ax.bluestein) {
-        return fail(ERR_UNSUPPORTED, "real z pass without a native or Bluestein plan");      // (dfft_init rules this out)
-    } else if (ax.longb) {
-        if (long_bytes(A, p->TL, ax.M, p->esz) > p->lv_bytes) return fail(ERR_STATE, "long Bluestein pass: scratch region too small");
-        return launch_long_bluestein(p->prec, ax, A, mode, p->Nzc, static_cast<char *>(p->work_d) + p->lv_off, p->TL, stream);
-    } else if (ax.two) {
-        if (two_level_bytes(A, p->TL, ax.N, p->esz) > p->lv_bytes) return fail(ERR_STATE, "two-level pass: scratch region too small");
-        return launch_two_level(p->prec, ax, A, mode, p->Nzc, static_cast<char *>(p->work_d) + p->lv_off, p->TL, stream);
-    } else {
-        A.NK = (uint32_t)p->Nzc; A.real_mode = mode;
-        r = launch_generic(p->prec, ax, A, stream);
-    }
-    if (r == -1) return fail(ERR_UNSUPPORTED, "unsupported real line length " + std::to_string(p->Nz));
-    if (r != 0) return fail(r, std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)r));
     return 0;
 }
 
@@ -482,379 +458,103 @@ static hipEvent_t pipe_event(dfft_plan *p, size_t i)
     }
     return pl.ev[i];
 }
-#define EV_RECORD(i, stream) do { hipEvent_t pev_ = pipe_event(p, (i)); if (!pev_) return fail(1, "hipEventCreate failed"); HIP_TRY(hipEventRecord(pev_, (stream))); } while (0)
-#define EV_WAIT(i, stream) do { HIP_TRY(hipStreamWaitEvent((stream), pipe_event(p, (i)), 0)); } while (0)
 
-// forward chain.  Buffers: A = caller's out, W0..W2 = work area slices (one per exchange + 1).
-//   z: in -> A   [ex1: A -> W0]   y: -> next   [ex2: -> next]   x: -> A
-static int enqueue_forward_zyx(dfft_plan *p, void *out, const void *in);
-static int enqueue_forward_yzx(dfft_plan *p, void *out, const void *in);
-static int enqueue_inverse_zyx(dfft_plan *p, void *out, void *in);
-
-// one rank, complex, pass order z, x, y (build_pipeline_single).  Forward and inverse are the same three launches,
-// the inverse with conjugation:   z: in -> out (L1)   x: out -> W (L2)   y: W -> out
-static int enqueue_single(dfft_plan *p, void *out, const void *in, int swap)
+// the chain an exec of `dims` dimensions (3: the whole transform) in `direction` runs now
+static const Chain &chain_of(const dfft_plan *p, int direction, int dims)
 {
-    Pipeline &pl = p->pl;
-    char *O = static_cast<char *>(out), *W = static_cast<char *>(p->work_d);
-    const char *I = static_cast<const char *>(in);
-    hipStream_t Sc = p->stream;
-    p->nspans = 0; p->last_dir = swap ? DFFT_INVERSE : DFFT_FORWARD;
-    auto run = [&](const Launch &L, int variant, int axis, const char *src, char *dst, int phase) -> int {
-        Launch M = L;
-        M.args.swap = swap;
-        TRY(span_begin(p, phase, Sc));
-        TRY(launch(p, M, variant, axis, src, dst));
-        TRY(span_end(p, Sc));
-        return 0;
-    };
-    // phase slots follow the axis (0 z, 2 y, 4 x in forward naming; mirrored for the inverse naming) so that the
-    // per-phase report keeps its labels
-    TRY(run(pl.sz, p->vfwd[0], 0, I, O, swap ? 4 : 0));
-    TRY(run(pl.sx, p->vfwd[2], 2, O, W, swap ? 0 : 4));
-    TRY(run(pl.sy, p->vfwd[1], 1, W, O, 2));
-    return 0;
+    const Pipeline &pl = p->pl;
+    const bool fwd = direction != DFFT_INVERSE;
+    if (dims == 3 && one_rank_alternative(p) && !(fwd ? pl.one_fwd : pl.one_inv).steps.empty()) return fwd ? pl.one_fwd : pl.one_inv;
+    return fwd ? pl.fwd[dims - 1] : pl.inv[dims - 1];
 }
 
-static int enqueue_forward(dfft_plan *p, void *out, const void *in)
+std::vector<Launch> *pass_launches(dfft_plan *p, int k)
 {
-    if (p->zyx) return enqueue_forward_zyx(p, out, in);
-    if (p->yzx) return enqueue_forward_yzx(p, out, in);
-    if (p->pl.single && !p->opt.mirror && !p->spectral_mirror) return enqueue_single(p, out, in, 0);
-    Pipeline &pl = p->pl;
-    const int C = pl.C;
-    char *A = static_cast<char *>(out), *W = static_cast<char *>(p->work_d);
-    const char *I = static_cast<const char *>(in);
-    int nextw = 0;
-    auto next_work = [&]() { return W + (size_t)(nextw++) * p->domainsize; };
-    char *zdst = A;
-    char *ysrc = p->P2 > 1 ? next_work() : A;
-    char *ydst = next_work();
-    char *xsrc = p->P1 > 1 ? next_work() : ydst;
-    hipStream_t Sc = p->stream, Sm = pl.comm_stream;
-    // exchange 2 of a pencil plan runs on its own stream (row and column groups use disjoint links)
-    hipStream_t Sm2 = (pl.comm_stream2 && p->comm && p->comm->concurrent_channels()) ? pl.comm_stream2 : Sm;
-    p->nspans = 0; p->last_dir = DFFT_FORWARD;
-    // two compute streams (option compute_streams): chunk c of a pass runs on SC(c); a chunk depends on the same chunk of the pass
-    // (or exchange) before it, which sits on the same stream or arrives through that chunk's event
-    hipStream_t Sc2 = (compute_streams_of(p) > 1 && !p->lv_bytes) ? pl.compute_stream2 : nullptr;     // (two-level passes share one scratch)
-    auto SC = [&](int c) { return (Sc2 && (c & 1)) ? Sc2 : Sc; };
-    // event ids: [0,C) z done, [C,2C) ex1 done, [2C,3C) y done, [3C,4C) ex2 done, 4C = entry fence, 4C+1.. = joins of the compute streams
-    if ((p->comm && p->nranks > 1) || Sc2) EV_RECORD(4 * C, Sc);
-    if (p->comm && p->nranks > 1) { EV_WAIT(4 * C, Sm); if (Sm2 != Sm) EV_WAIT(4 * C, Sm2); }   // comm streams start after prior work
-    if (Sc2) EV_WAIT(4 * C, Sc2);
-    auto zpass = [&](int c) -> int {
-        hipStream_t Sc = SC(c);
-        TRY(span_begin(p, 0, Sc));
-        if (p->c2c) TRY(launch(p, pl.fz[c], p->vfwd[0], 0, I, zdst, false, Sc));
-        else TRY(launch_real(p, pl.fz[c], 1, I, zdst, Sc));
-        TRY(span_end(p, Sc));
-        if (p->P2 > 1) {
-            EV_RECORD(c, Sc);
-            EV_WAIT(c, Sm);
-            TRY(span_begin(p, 1, Sm));
-            TRY(exchange_tables(p, 1, pl.f1[c], true, zdst, ysrc, Sm, 0, pipe_event(p, c)));
-            TRY(span_end(p, Sm));
-            EV_RECORD(C + c, Sm);
-        }
-        return 0;
-    };
-    auto ypass = [&](int c) -> int {
-        hipStream_t Sc = SC(c);
-        if (p->P2 > 1) EV_WAIT(C + c, Sc);
-        TRY(span_begin(p, 2, Sc));
-        TRY(launch(p, pl.fy[c], p->vfwd[1], 1, ysrc, ydst, false, Sc));
-        TRY(span_end(p, Sc));
-        if (p->P1 > 1) {
-            EV_RECORD(2 * C + c, Sc);
-            EV_WAIT(2 * C + c, Sm2);
-            TRY(span_begin(p, 3, Sm2));
-            TRY(exchange_tables(p, 2, pl.f2[c], true, ydst, xsrc, Sm2, 0, pipe_event(p, 2 * C + c)));
-            TRY(span_end(p, Sm2));
-            EV_RECORD(3 * C + c, Sm2);
-        }
-        return 0;
-    };
-    if (p->P2 > 1) {
-        // pencil: all z chunks first, so that exchange 1 of chunk c overlaps z(c+1)
-        for (int c = 0; c < C; c++) TRY(zpass(c));
-        for (int c = 0; c < C; c++) TRY(ypass(c));
-    } else {
-        // slab (no exchange 1): y(c) only needs z(c); interleave so the first chunk reaches the
-        // wire after one z and one y chunk instead of after the whole z pass
-        for (int c = 0; c < C; c++) { TRY(zpass(c)); TRY(ypass(c)); }
-    }
-    if (p->P1 > 1) EV_WAIT(3 * C + C - 1, Sc);     // the comm stream is in order: last chunk covers all
-    else if (p->P2 > 1) { /* y passes already waited for every ex1 chunk */ }
-    if (Sc2) { EV_RECORD(4 * C + 1, Sc2); EV_WAIT(4 * C + 1, Sc); }      // the x pass (and the caller's stream) follow the odd chunks too
-    TRY(span_begin(p, 4, Sc));
-    TRY(launch(p, pl.fx, p->vfwd[2], 2, xsrc, A));
-    TRY(span_end(p, Sc));
-    return 0;
+    // the z, x, y order of a single rank names its z / y / x passes fz / fy / fx, and its inverse runs them again
+    static const int alt[6] = {G_SZ, G_SY, G_SX, -1, -1, -1};
+    const int g = p->pl.single && one_rank_alternative(p) ? alt[k] : k;      // (G_FZ .. G_IZ == 0 .. 5)
+    return g < 0 ? nullptr : &p->pl.groups[g].L;
 }
 
-// inverse chain.  `in` (I) is scratch once every x^-1 chunk has read it.
-//   x^-1: I -> W0   [ex2: W0 -> W1]   y^-1: -> I   [ex1: I -> W0]   z^-1: -> out
-static int enqueue_inverse(dfft_plan *p, void *out, void *in)
+// Runs one execution chain (Pipeline::fwd / inv / one_fwd / one_inv).  The streams and events follow from its steps:
+//  - chunk c of a step runs on compute stream c mod 2 where the chain may split and the plan uses two compute streams (never while
+//    two-level passes share their scratch); every other launch runs on the plan's stream
+//  - the exchange after chunk c runs on the communication stream of that exchange (2: comm_stream2 where the transport has concurrent
+//    channels) behind an event recorded after the chunk (the relay's `ready`: comm.hpp), and records the event its consumer waits for
+//  - chunk c of a step waits for the exchange of chunk c before it, or -- `whole` -- for all of the step before: the last exchange
+//    chunk (the communication stream is in order) and the other compute stream; steps that depend chunk by chunk without an exchange
+//    between them run interleaved, chunk c of the second right behind chunk c of the first
+//  - the communication streams start after the caller's prior work (entry fence), the caller's stream ends after the second compute stream
+static int run_chain(dfft_plan *p, int direction, int dims, void *out, const void *in)
 {
-    if (p->zyx) return enqueue_inverse_zyx(p, out, in);
-    if (p->yzx) return fail(ERR_UNSUPPORTED, "the Y_Then_ZX sequence is forward only (as in the reference)");
-    if (p->pl.single && !p->opt.mirror && !p->spectral_mirror) return enqueue_single(p, out, in, 1);
+    const Chain &ch = chain_of(p, direction, dims);
+    const std::vector<Step> &st = ch.steps;
+    if (st.empty()) return fail(ERR_UNSUPPORTED, "the Y_Then_ZX sequence is forward only (as in the reference)");
     Pipeline &pl = p->pl;
-    const int C = pl.C;
-    char *I = static_cast<char *>(in), *W = static_cast<char *>(p->work_d), *O = static_cast<char *>(out);
-    char *W0 = W, *W1 = W + p->domainsize;
-    char *xdst = W0;
-    char *ysrc = p->P1 > 1 ? W1 : W0;
-    char *ydst = I;
-    char *zsrc = p->P2 > 1 ? (p->P1 > 1 ? W0 : W1) : I;   // W0 is still read by y^-1 when there is no exchange 2
+    auto buf = [&](int b) {
+        return b == BUF_IN ? const_cast<char *>(static_cast<const char *>(in)) : b == BUF_OUT ? static_cast<char *>(out)
+                                                                               : static_cast<char *>(p->work_d) + (size_t)b * p->domainsize;
+    };
     hipStream_t Sc = p->stream, Sm = pl.comm_stream;
     hipStream_t Sm2 = (pl.comm_stream2 && p->comm && p->comm->concurrent_channels()) ? pl.comm_stream2 : Sm;
-    p->nspans = 0; p->last_dir = DFFT_INVERSE;
-    if (p->nranks == 1 && p->c2c && !p->opt.mirror && !p->spectral_mirror) {
-        // single rank, complex: input and output are both natural [x][y][z], so the inverse may use
-        // the forward pass order (z, y, x) with conjugation -- it avoids the strided *read* of the
-        // x-first order (the fft3d branch of the reference is one cuFFT plan, order is not observable)
-        auto conj_launch = [&](const Launch &L, int variant, int axis, const char *src, char *dst) -> int {
-            Launch M = L;
-            M.args.swap = 1;
-            return launch(p, M, variant, axis, src, dst);
-        };
-        for (int c = 0; c < C; c++) { TRY(span_begin(p, 4, Sc)); TRY(conj_launch(pl.fz[c], p->vfwd[0], 0, I, W0)); TRY(span_end(p, Sc)); }
-        for (int c = 0; c < C; c++) { TRY(span_begin(p, 2, Sc)); TRY(conj_launch(pl.fy[c], p->vfwd[1], 1, W0, I)); TRY(span_end(p, Sc)); }
-        TRY(span_begin(p, 0, Sc));
-        TRY(conj_launch(pl.fx, p->vfwd[2], 2, I, O));
-        TRY(span_end(p, Sc));
-        return 0;
-    }
-    hipStream_t Sc2 = (compute_streams_of(p) > 1 && !p->lv_bytes) ? pl.compute_stream2 : nullptr;     // (two-level passes share one scratch)
+    hipStream_t Sc2 = (ch.split && compute_streams_of(p) > 1 && !p->lv_bytes) ? pl.compute_stream2 : nullptr;     // (two-level passes share one scratch)
     auto SC = [&](int c) { return (Sc2 && (c & 1)) ? Sc2 : Sc; };
-    // both compute streams have finished what they were given so far (event ids 4C+1 ..: see enqueue_forward)
-    int joins = 0;
-    auto cross_join = [&]() -> int {
-        if (!Sc2) return 0;
-        const int a = 4 * C + 1 + 2 * joins++;
-        EV_RECORD(a, Sc2); EV_RECORD(a + 1, Sc);
-        EV_WAIT(a, Sc); EV_WAIT(a + 1, Sc2);
+    p->nspans = 0; p->last_dir = direction == DFFT_INVERSE ? DFFT_INVERSE : DFFT_FORWARD;
+    size_t nev = 0;     // events of this exec, in order of use
+    auto record = [&](hipStream_t s, hipEvent_t &e) -> int {
+        e = pipe_event(p, nev++);
+        if (!e) return fail(1, "hipEventCreate failed");
+        HIP_TRY(hipEventRecord(e, s));
         return 0;
     };
-    if ((p->comm && p->nranks > 1) || Sc2) EV_RECORD(4 * C, Sc);
-    if (p->comm && p->nranks > 1) { EV_WAIT(4 * C, Sm); if (Sm2 != Sm) EV_WAIT(4 * C, Sm2); }
-    if (Sc2) EV_WAIT(4 * C, Sc2);
-    for (int c = 0; c < C; c++) {
-        hipStream_t Sc = SC(c);
-        TRY(span_begin(p, 0, Sc));
-        TRY(launch(p, pl.ix[c], p->vinv[2], 2, I, xdst, false, Sc));
-        TRY(span_end(p, Sc));
-        if (p->P1 > 1) {
-            EV_RECORD(c, Sc);
-            EV_WAIT(c, Sm2);
-            TRY(span_begin(p, 1, Sm2));
-            TRY(exchange_tables(p, 2, pl.i2[c], true, xdst, ysrc, Sm2, 0, pipe_event(p, c)));    // i2/i1 tables are already in send/recv order
-            TRY(span_end(p, Sm2));
-            EV_RECORD(C + c, Sm2);
+    auto wait = [&](hipEvent_t e, hipStream_t s) -> int { HIP_TRY(hipStreamWaitEvent(s, e, 0)); return 0; };
+    auto join = [&](hipStream_t from, hipStream_t to) -> int { hipEvent_t e; TRY(record(from, e)); return wait(e, to); };
+    const bool comm = p->comm && p->nranks > 1 && st.size() > 1;
+    bool ex2 = false;
+    for (const Step &s : st) ex2 = ex2 || s.xchg == 2;
+    hipEvent_t fence = nullptr;
+    if (comm || Sc2) TRY(record(Sc, fence));
+    if (comm) { TRY(wait(fence, Sm)); if (ex2 && Sm2 != Sm) TRY(wait(fence, Sm2)); }
+    if (Sc2) TRY(wait(fence, Sc2));
+    hipEvent_t xdone[MAXSEG];     // exchange of chunk c of the step before is complete
+    int xprev = 0, xn = 0;        // ... which exchange that was (0: none), after how many chunks
+    for (size_t s0 = 0, s1; s0 < st.size(); s0 = s1) {
+        for (s1 = s0 + 1; s1 < st.size() && !st[s1].whole && !st[s1 - 1].xchg; s1++) {}      // steps [s0, s1) run interleaved
+        const Step &first = st[s0];
+        const int nchunk = (int)(pl.groups[first.group].L.size() / first.per_chunk);
+        const bool spread = Sc2 && nchunk > 1;      // on both compute streams
+        if (first.whole) {
+            if (spread) {      // both compute streams have finished what they were given so far
+                hipEvent_t a, b;
+                TRY(record(Sc2, a)); TRY(record(Sc, b)); TRY(wait(a, Sc)); TRY(wait(b, Sc2));
+            }
+            if (xprev) { TRY(wait(xdone[xn - 1], Sc)); if (spread) TRY(wait(xdone[xn - 1], Sc2)); }
+            if (Sc2 && !spread) TRY(join(Sc2, Sc));
         }
-    }
-    // y^-1 needs complete ky lines: every chunk of exchange 2 must have landed.  It also
-    // overwrites I, which every x^-1 chunk has read by now (same stream).
-    TRY(cross_join());      // ... on either stream
-    if (p->P1 > 1) { EV_WAIT(C + C - 1, Sc); if (Sc2) EV_WAIT(C + C - 1, Sc2); }
-    for (int c = 0; c < C; c++) {
-        hipStream_t Sc = SC(c);
-        TRY(span_begin(p, 2, Sc));
-        TRY(launch(p, pl.iy[c], p->vinv[1], 1, ysrc, ydst, false, Sc));
-        TRY(span_end(p, Sc));
-        if (p->P2 > 1) {
-            EV_RECORD(2 * C + c, Sc);
-            EV_WAIT(2 * C + c, Sm);
-            TRY(span_begin(p, 3, Sm));
-            TRY(exchange_tables(p, 1, pl.i1[c], true, ydst, zsrc, Sm, 0, pipe_event(p, 2 * C + c)));
-            TRY(span_end(p, Sm));
-            EV_RECORD(3 * C + c, Sm);
+        for (int c = 0; c < nchunk; c++) {
+            hipStream_t S = SC(c);
+            if (!first.whole && xprev) TRY(wait(xdone[c], S));
+            for (size_t i = s0; i < s1; i++) {
+                const Step &t = st[i];
+                const Group &g = pl.groups[t.group];
+                if (t.phase >= 0) TRY(span_begin(p, t.phase, S));
+                for (int k = c * t.per_chunk; k < (c + 1) * t.per_chunk; k++) TRY(launch(p, g.L[k], t.form, g.axis, t.conj, buf(t.src), buf(t.dst), S));
+                if (t.phase >= 0) TRY(span_end(p, S));
+            }
+            const Step &t = st[s1 - 1];
+            if (t.xchg) {
+                const std::vector<A2A> &T = direction == DFFT_INVERSE ? (t.xchg == 1 ? pl.i1 : pl.i2) : (t.xchg == 1 ? pl.f1 : pl.f2);
+                hipStream_t Sx = t.xchg == 1 ? Sm : Sm2;
+                hipEvent_t ready;
+                TRY(record(S, ready)); TRY(wait(ready, Sx));
+                if (t.phase >= 0) TRY(span_begin(p, t.phase + 1, Sx));
+                TRY(exchange_tables(p, t.xchg, T[c], true, buf(t.dst), buf(st[s1].src), Sx, 0, ready));      // (tables in send / receive order)
+                if (t.phase >= 0) TRY(span_end(p, Sx));
+                TRY(record(Sx, xdone[c]));
+            }
         }
-    }
-    if (p->P2 == 1) TRY(cross_join());      // no exchange 1 between y^-1 and z^-1: the chunks of the two passes need not coincide
-    for (int c = 0; c < C; c++) {
-        hipStream_t Sc = SC(c);
-        if (p->P2 > 1) EV_WAIT(3 * C + c, Sc);
-        TRY(span_begin(p, 4, Sc));
-        if (p->c2c) TRY(launch(p, pl.iz[c], p->vinv[0], 0, zsrc, O, false, Sc));
-        else TRY(launch_real(p, pl.iz[c], 2, zsrc, O, Sc));
-        TRY(span_end(p, Sc));
-    }
-    if (Sc2) { const int a = 4 * C + 1 + 2 * joins; EV_RECORD(a, Sc2); EV_WAIT(a, Sc); }      // the caller's stream follows the odd chunks
-    return 0;
-}
-
-
-// Z_Then_YX forward:  z: in -> A   [ex: A -> W0]   y: W0 -> W1   x: W1 -> A
-// (src/slab/z_then_yx/mpicufft_slab_z_then_yx.cpp execR2C: 1-D R2C, all-to-all, 2-D C2C)
-static int enqueue_forward_zyx(dfft_plan *p, void *out, const void *in)
-{
-    Pipeline &pl = p->pl;
-    const int C = pl.C, P = p->P1;
-    char *A = static_cast<char *>(out), *W = static_cast<char *>(p->work_d);
-    const char *I = static_cast<const char *>(in);
-    char *ysrc = P > 1 ? W : A;
-    char *ydst = P > 1 ? W + p->domainsize : W;
-    hipStream_t Sc = p->stream, Sm = pl.comm_stream;
-    p->nspans = 0; p->last_dir = DFFT_FORWARD;
-    if (p->comm && P > 1) { EV_RECORD(4 * C, Sc); EV_WAIT(4 * C, Sm); }
-    for (int c = 0; c < C; c++) {
-        TRY(span_begin(p, 0, Sc));
-        if (p->c2c) TRY(launch(p, pl.fz[c], p->vfwd[0], 0, I, A));
-        else TRY(launch_real(p, pl.fz[c], 1, I, A));
-        TRY(span_end(p, Sc));
-        if (P > 1) {
-            EV_RECORD(c, Sc);
-            EV_WAIT(c, Sm);
-            TRY(span_begin(p, 1, Sm));
-            TRY(exchange_tables(p, 2, pl.f2[c], true, A, ysrc, Sm));
-            TRY(span_end(p, Sm));
-            EV_RECORD(C + c, Sm);
-        }
-    }
-    for (int c = 0; c < C; c++) {
-        if (P > 1) EV_WAIT(C + c, Sc);
-        TRY(span_begin(p, 2, Sc));
-        for (int q = 0; q < P; q++) TRY(launch(p, pl.zy[(size_t)c * P + q], p->vfwd[1], 1, ysrc, ydst));
-        TRY(span_end(p, Sc));
-    }
-    TRY(span_begin(p, 4, Sc));
-    TRY(launch(p, pl.fx, p->vfwd[2], 2, ydst, A));
-    TRY(span_end(p, Sc));
-    return 0;
-}
-
-// Z_Then_YX inverse:  x^-1: I -> W0   y^-1: W0 -> I   [ex: I -> W1]   z^-1: -> out
-static int enqueue_inverse_zyx(dfft_plan *p, void *out, void *in)
-{
-    Pipeline &pl = p->pl;
-    const int C = pl.C, P = p->P1;
-    char *I = static_cast<char *>(in), *W = static_cast<char *>(p->work_d), *O = static_cast<char *>(out);
-    char *zsrc = P > 1 ? W + p->domainsize : I;
-    hipStream_t Sc = p->stream, Sm = pl.comm_stream;
-    p->nspans = 0; p->last_dir = DFFT_INVERSE;
-    if (p->comm && P > 1) { EV_RECORD(4 * C, Sc); EV_WAIT(4 * C, Sm); }
-    TRY(span_begin(p, 0, Sc));
-    TRY(launch(p, pl.zix, p->vinv[2], 2, I, W));
-    TRY(span_end(p, Sc));
-    for (int c = 0; c < C; c++) {
-        TRY(span_begin(p, 2, Sc));
-        for (int q = 0; q < P; q++) TRY(launch(p, pl.ziy[(size_t)c * P + q], p->vinv[1], 1, W, I));
-        TRY(span_end(p, Sc));
-        if (P > 1) {
-            EV_RECORD(c, Sc);
-            EV_WAIT(c, Sm);
-            TRY(span_begin(p, 3, Sm));
-            TRY(exchange_tables(p, 2, pl.i2[c], true, I, zsrc, Sm));
-            TRY(span_end(p, Sm));
-            EV_RECORD(C + c, Sm);
-        }
-    }
-    for (int c = 0; c < C; c++) {
-        if (P > 1) EV_WAIT(C + c, Sc);
-        TRY(span_begin(p, 4, Sc));
-        if (p->c2c) TRY(launch(p, pl.iz[c], p->vinv[0], 0, zsrc, O));
-        else TRY(launch_real(p, pl.iz[c], 2, zsrc, O));
-        TRY(span_end(p, Sc));
-    }
-    return 0;
-}
-
-// Y_Then_ZX forward:  y: in -> A   [ex: A -> W0]   x: W0 -> W1   z: W1 -> A
-static int enqueue_forward_yzx(dfft_plan *p, void *out, const void *in)
-{
-    Pipeline &pl = p->pl;
-    const int C = pl.C, P = p->P1;
-    char *A = static_cast<char *>(out), *W = static_cast<char *>(p->work_d);
-    const char *I = static_cast<const char *>(in);
-    char *xsrc = P > 1 ? W : A;
-    char *xdst = P > 1 ? W + p->domainsize : W;
-    hipStream_t Sc = p->stream, Sm = pl.comm_stream;
-    p->nspans = 0; p->last_dir = DFFT_FORWARD;
-    if (p->comm && P > 1) { EV_RECORD(4 * C, Sc); EV_WAIT(4 * C, Sm); }
-    for (int c = 0; c < C; c++) {
-        TRY(span_begin(p, 0, Sc));
-        TRY(launch(p, pl.fy[c], p->vfwd[1], 1, I, A, !p->c2c));
-        TRY(span_end(p, Sc));
-        if (P > 1) {
-            EV_RECORD(c, Sc);
-            EV_WAIT(c, Sm);
-            TRY(span_begin(p, 1, Sm));
-            TRY(exchange_tables(p, 2, pl.f2[c], true, A, xsrc, Sm));
-            TRY(span_end(p, Sm));
-            EV_RECORD(C + c, Sm);
-        }
-    }
-    if (P > 1) EV_WAIT(C + C - 1, Sc);
-    TRY(span_begin(p, 2, Sc));
-    TRY(launch(p, pl.fx, p->vfwd[2], 2, xsrc, xdst));
-    TRY(span_end(p, Sc));
-    TRY(span_begin(p, 4, Sc));
-    TRY(launch(p, pl.yz, 0, 0, xdst, A));
-    TRY(span_end(p, Sc));
-    return 0;
-}
-
-// partial transforms of the reference's MPIcuFFT_Pencil::execR2C/execC2R(out, in, d)
-// (src/pencil/mpicufft_pencil.cpp:1644-1839): d = 1 stops after the z pass with the natural
-// stage layout [xs][ys][Nzc]; d = 2 stops after the y pass with [xs][Ny][zs] (z contiguous).
-static int enqueue_partial_forward(dfft_plan *p, void *out, const void *in, int d)
-{
-    Pipeline &pl = p->pl;
-    const int C = pl.C;
-    const char *I = static_cast<const char *>(in);
-    char *O = static_cast<char *>(out), *W = static_cast<char *>(p->work_d);
-    hipStream_t Sc = p->stream, Sm = pl.comm_stream;
-    p->nspans = 0; p->last_dir = DFFT_FORWARD;
-    if (d == 1) {
-        if (p->c2c) return launch(p, pl.pz1, p->vfwd[0], 0, I, O);
-        return launch_real(p, pl.pz1, 1, I, O);
-    }
-    char *zdst = W, *ysrc = p->P2 > 1 ? W + p->domainsize : W;
-    if (p->comm && p->nranks > 1) { EV_RECORD(4 * C, Sc); EV_WAIT(4 * C, Sm); }
-    for (int c = 0; c < C; c++) {
-        if (p->c2c) TRY(launch(p, pl.fz[c], p->vfwd[0], 0, I, zdst));
-        else TRY(launch_real(p, pl.fz[c], 1, I, zdst));
-        if (p->P2 > 1) {
-            EV_RECORD(c, Sc); EV_WAIT(c, Sm);
-            TRY(exchange_tables(p, 1, pl.f1[c], true, zdst, ysrc, Sm, 0, pipe_event(p, c)));
-            EV_RECORD(C + c, Sm);
-        }
-    }
-    for (int c = 0; c < C; c++) {
-        if (p->P2 > 1) EV_WAIT(C + c, Sc);
-        TRY(launch(p, pl.py2[c], p->vfwd[1], 1, ysrc, O));
-    }
-    return 0;
-}
-
-static int enqueue_partial_inverse(dfft_plan *p, void *out, void *in, int d)
-{
-    Pipeline &pl = p->pl;
-    const int C = pl.C;
-    char *I = static_cast<char *>(in), *O = static_cast<char *>(out), *W = static_cast<char *>(p->work_d);
-    hipStream_t Sc = p->stream, Sm = pl.comm_stream;
-    p->nspans = 0; p->last_dir = DFFT_INVERSE;
-    if (d == 1) {
-        if (p->c2c) return launch(p, pl.qz1, p->vinv[0], 0, I, O);
-        return launch_real(p, pl.qz1, 2, I, O);
-    }
-    char *ydst = W, *zsrc = p->P2 > 1 ? W + p->domainsize : W;
-    if (p->comm && p->nranks > 1) { EV_RECORD(4 * C, Sc); EV_WAIT(4 * C, Sm); }
-    for (int c = 0; c < C; c++) {
-        TRY(launch(p, pl.qy2[c], p->vinv[1], 1, I, ydst));
-        if (p->P2 > 1) {
-            EV_RECORD(c, Sc); EV_WAIT(c, Sm);
-            TRY(exchange_tables(p, 1, pl.i1[c], true, ydst, zsrc, Sm, 0, pipe_event(p, c)));
-            EV_RECORD(C + c, Sm);
-        }
-    }
-    for (int c = 0; c < C; c++) {
-        if (p->P2 > 1) EV_WAIT(C + c, Sc);
-        if (p->c2c) TRY(launch(p, pl.iz[c], p->vinv[0], 0, zsrc, O));
-        else TRY(launch_real(p, pl.iz[c], 2, zsrc, O));
+        xprev = st[s1 - 1].xchg; xn = nchunk;
+        if (s1 == st.size() && spread) TRY(join(Sc2, Sc));      // the caller's stream follows the odd chunks
     }
     return 0;
 }
@@ -1235,18 +935,13 @@ int dfft_init(dfft_plan *p, size_t Nx, size_t Ny, size_t Nz, int P1, int P2, int
     }
     {   // two-level axes: the scratch between the levels is a region of the work area behind the exchange slices, sized for the
         // largest launch (tiles x TL lines x N points)
-        const Pipeline &pl = p->pl;
         size_t lvb = 0;
-        auto need = [&](const Launch &L, int axis) {
-            if (p->ax[axis].two) lvb = std::max(lvb, two_level_bytes(L.args, p->TL, p->ax[axis].N, p->esz));
-            if (p->ax[axis].longb) lvb = std::max(lvb, long_bytes(L.args, p->TL, p->ax[axis].M, p->esz));
-        };
-        for (auto &L : pl.fz) need(L, 0); for (auto &L : pl.iz) need(L, 0);
-        for (auto &L : pl.fy) need(L, 1); for (auto &L : pl.iy) need(L, 1); for (auto &L : pl.py2) need(L, 1); for (auto &L : pl.qy2) need(L, 1);
-        for (auto &L : pl.zy) need(L, 1); for (auto &L : pl.ziy) need(L, 1);
-        for (auto &L : pl.ix) need(L, 2);
-        need(pl.fx, 2); need(pl.zix, 2); need(pl.pz1, 0); need(pl.qz1, 0); need(pl.yz, 0);
-        if (pl.single) { need(pl.sz, 0); need(pl.sx, 2); need(pl.sy, 1); }
+        for (const Group &g : p->pl.groups)
+            for (const Launch &L : g.L) {
+                const Axis &a = p->ax[g.axis];
+                if (a.two) lvb = std::max(lvb, two_level_bytes(L.args, p->TL, a.N, p->esz));
+                if (a.longb) lvb = std::max(lvb, long_bytes(L.args, p->TL, a.M, p->esz));
+            }
         p->worksize_d = (p->worksize_d + 255) & ~(size_t)255;
         p->lv_off = p->worksize_d;
         p->lv_bytes = (lvb + 255) & ~(size_t)255;
@@ -1302,21 +997,11 @@ int dfft_init(dfft_plan *p, size_t Nx, size_t Ny, size_t Nz, int P1, int P2, int
             // 2048 points 10.55 vs 10.35, no better -- L2 merges the pieces; profiles/r3_f32_inverse_y_point_fastest_store.txt.)
         }
     }
-    {   // per-pass overrides (dfft_set_option): fz fy fx ix iy iz
-        Pipeline &pl = p->pl;
-        std::vector<Launch> *vecs[6] = {&pl.fz, &pl.fy, nullptr, &pl.ix, &pl.iy, &pl.iz};
-        for (int k = 0; k < 6; k++) {
-            const int d = p->opt.order[k];
-            if (d >= 0) {
-                auto set = [&](Launch &L) { L.args.a_fastest = d & 1; L.args.xcd_swizzle = (d >> 1) & 1; };
-                if (k == 2) set(pl.fx); else for (auto &L : *vecs[k]) set(L);
-            }
-            if (p->opt.variant[k] >= 0) (k < 3 ? p->vfwd[k] : p->vinv[5 - k]) = p->opt.variant[k];
-            if (d >= 0 && pl.single && k < 3) {      // the z, x, y order of a single rank: fz / fy / fx name its z / y / x passes
-                Launch &L = k == 0 ? pl.sz : k == 1 ? pl.sy : pl.sx;
-                L.args.a_fastest = d & 1; L.args.xcd_swizzle = (d >> 1) & 1;
-            }
-        }
+    for (int k = 0; k < 6; k++) {      // per-pass overrides (dfft_set_option): fz fy fx ix iy iz
+        const int d = p->opt.order[k];
+        if (std::vector<Launch> *v = d >= 0 ? pass_launches(p, k) : nullptr)
+            for (Launch &L : *v) { L.args.a_fastest = d & 1; L.args.xcd_swizzle = (d >> 1) & 1; }
+        if (p->opt.variant[k] >= 0) (k < 3 ? p->vfwd[k] : p->vinv[5 - k]) = p->opt.variant[k];
     }
     for (auto &a : p->ax) axis_free(a);
     for (void **t : {&p->tw_zr, &p->tables_d}) if (*t) { (void)hipFree(*t); *t = nullptr; }
@@ -1362,9 +1047,7 @@ static int upload_tables(dfft_plan *p)
     // more than one segment (default), 2 = tables for every tiled load / store
     const int mode = p->opt.tables;
     std::vector<Launch *> all;
-    for (auto *v : {&pl.fz, &pl.fy, &pl.ix, &pl.iy, &pl.iz, &pl.py2, &pl.qy2, &pl.zy, &pl.ziy}) for (auto &L : *v) all.push_back(&L);
-    all.push_back(&pl.fx); all.push_back(&pl.pz1); all.push_back(&pl.qz1); all.push_back(&pl.zix); all.push_back(&pl.yz);
-    if (pl.single) { all.push_back(&pl.sz); all.push_back(&pl.sx); all.push_back(&pl.sy); }
+    for (Group &g : pl.groups) for (Launch &L : g.L) all.push_back(&L);
     std::vector<char> host(all.size() * 2 * sizeof(SegTable));
     size_t off = 0;
     for (Launch *L : all) {
@@ -1460,8 +1143,8 @@ int dfft_enqueue_c2c(dfft_plan *p, void *out, void *in, int direction)
     TRY(check_ready(p));
     if (!p->c2c) return fail(ERR_STATE, "plan was initialised for R2C/C2R");
     if (!out || !in) return fail(ERR_ARG, "null buffer");
-    if (direction == DFFT_FORWARD) return run_graphed(p, 0, in, out, [&]() { return enqueue_forward(p, out, in); });
-    if (direction == DFFT_INVERSE) return run_graphed(p, 1, in, out, [&]() { return enqueue_inverse(p, out, in); });
+    if (direction == DFFT_FORWARD || direction == DFFT_INVERSE)
+        return run_graphed(p, direction == DFFT_INVERSE, in, out, [&]() { return run_chain(p, direction, 3, out, in); });
     return fail(ERR_ARG, "direction must be DFFT_FORWARD or DFFT_INVERSE");
 }
 
@@ -1480,10 +1163,7 @@ int dfft_exec_dim(dfft_plan *p, void *out, void *in, int direction, int d)
     if (direction != DFFT_FORWARD && direction != DFFT_INVERSE) return fail(ERR_ARG, "bad direction");
     if ((p->zyx || p->yzx) && d != 3) return fail(ERR_UNSUPPORTED, "partial transforms are not defined for the Z_Then_YX / Y_Then_ZX sequences");
     const int kind = 2 * d + (direction == DFFT_INVERSE ? 1 : 0) + 8;
-    TRY(run_graphed(p, kind, in, out, [&]() {
-        if (d == 3) return direction == DFFT_FORWARD ? enqueue_forward(p, out, in) : enqueue_inverse(p, out, in);
-        return direction == DFFT_FORWARD ? enqueue_partial_forward(p, out, in, d) : enqueue_partial_inverse(p, out, in, d);
-    }));
+    TRY(run_graphed(p, kind, in, out, [&]() { return run_chain(p, direction, d, out, in); }));
     HIP_TRY(hipStreamSynchronize(p->stream));
     return 0;
 }
@@ -1510,7 +1190,7 @@ int dfft_exec_r2c(dfft_plan *p, void *out, const void *in)
     TRY(check_ready(p));
     if (p->c2c) return fail(ERR_STATE, "plan was initialised for C2C");
     if (!out || !in) return fail(ERR_ARG, "null buffer");
-    TRY(run_graphed(p, 2, in, out, [&]() { return enqueue_forward(p, out, in); }));
+    TRY(run_graphed(p, 2, in, out, [&]() { return run_chain(p, DFFT_FORWARD, 3, out, in); }));
     HIP_TRY(hipStreamSynchronize(p->stream));
     return 0;
 }
@@ -1519,7 +1199,7 @@ int dfft_exec_c2r(dfft_plan *p, void *out, void *in)
     TRY(check_ready(p));
     if (p->c2c) return fail(ERR_STATE, "plan was initialised for C2C");
     if (!out || !in) return fail(ERR_ARG, "null buffer");
-    TRY(run_graphed(p, 3, in, out, [&]() { return enqueue_inverse(p, out, in); }));
+    TRY(run_graphed(p, 3, in, out, [&]() { return run_chain(p, DFFT_INVERSE, 3, out, in); }));
     HIP_TRY(hipStreamSynchronize(p->stream));
     return 0;
 }
@@ -1618,29 +1298,8 @@ int dfft_get_pipeline_tables(const dfft_plan *p, int direction, int which, int c
 
 static const Launch *find_launch(const dfft_plan *p, const char *name, int index)
 {
-    const Pipeline &pl = p->pl;
-    const std::string n = name ? name : "";
-    auto at = [&](const std::vector<Launch> &v) -> const Launch * {
-        return index >= 0 && (size_t)index < v.size() ? &v[(size_t)index] : nullptr;
-    };
-    if (n == "fz") return at(pl.fz);
-    if (n == "fy") return at(pl.fy);
-    if (n == "ix") return at(pl.ix);
-    if (n == "iy") return at(pl.iy);
-    if (n == "iz") return at(pl.iz);
-    if (n == "py2") return at(pl.py2);
-    if (n == "qy2") return at(pl.qy2);
-    if (n == "zy") return at(pl.zy);
-    if (n == "ziy") return at(pl.ziy);
-    if (index != 0) return nullptr;
-    if (n == "fx") return &pl.fx;
-    if (n == "zix") return p->zyx ? &pl.zix : nullptr;
-    if (n == "yz") return p->yzx ? &pl.yz : nullptr;
-    if (n == "sz") return pl.single ? &pl.sz : nullptr;
-    if (n == "sx") return pl.single ? &pl.sx : nullptr;
-    if (n == "sy") return pl.single ? &pl.sy : nullptr;
-    if (n == "pz1") return &pl.pz1;
-    if (n == "qz1") return &pl.qz1;
+    for (const Group &g : p->pl.groups)
+        if (name && !strcmp(g.name, name)) return index >= 0 && (size_t)index < g.L.size() ? &g.L[(size_t)index] : nullptr;
     return nullptr;
 }
 
@@ -1663,17 +1322,30 @@ int dfft_debug_get_pass(const dfft_plan *p, const char *name, int index, dfft_pa
     return 0;
 }
 
+int dfft_debug_get_chain(const dfft_plan *p, int direction, int dims, dfft_chain_step *steps, int capacity, int *count)
+{
+    if (!p || !p->initialized) return fail(ERR_STATE, "plan not initialised");
+    if (dims < 1 || dims > 3 || (direction != DFFT_FORWARD && direction != DFFT_INVERSE)) return fail(ERR_ARG, "bad direction or dims");
+    const std::vector<Step> &st = chain_of(p, direction, dims).steps;
+    if (count) *count = (int)st.size();
+    for (size_t i = 0; i < st.size() && (int)i < capacity; i++) {
+        const Step &s = st[i];
+        const Group &g = p->pl.groups[s.group];
+        dfft_chain_step &d = steps[i];
+        memset(&d, 0, sizeof(d));
+        strncpy(d.group, g.name, sizeof(d.group) - 1);
+        d.axis = g.axis; d.launches = (int32_t)g.L.size(); d.per_chunk = s.per_chunk;
+        d.src = s.src; d.dst = s.dst; d.conj = s.conj; d.form = s.form; d.exchange = s.xchg;
+    }
+    return 0;
+}
+
 int dfft_get_pass_choices(const dfft_plan *p, int variant[6], int order[6], int addr64[6])
 {
     if (!p || !p->initialized) return fail(ERR_STATE, "plan not initialised");
-    const Pipeline &pl = p->pl;
-    const bool single = pl.single && p->nranks == 1 && !p->opt.mirror && !p->spectral_mirror && p->c2c;
-    const std::vector<Launch> *vecs[6] = {&pl.fz, &pl.fy, nullptr, &pl.ix, &pl.iy, &pl.iz};
     for (int k = 0; k < 6; k++) {
-        const Launch *L = nullptr;
-        if (single) L = k == 0 ? &pl.sz : k == 1 ? &pl.sy : k == 2 ? &pl.sx : nullptr;
-        else if (k == 2) L = &pl.fx;
-        else if (!vecs[k]->empty()) L = &(*vecs[k])[0];
+        const std::vector<Launch> *v = pass_launches(const_cast<dfft_plan *>(p), k);
+        const Launch *L = v && !v->empty() ? &(*v)[0] : nullptr;
         if (variant) variant[k] = k < 3 ? p->vfwd[k] : p->vinv[5 - k];
         if (order) order[k] = L ? (L->args.a_fastest ? 1 : 0) + (L->args.xcd_swizzle ? 2 : 0) : -1;
         if (addr64) addr64[k] = L ? L->args.addr64 : -1;

@@ -50,6 +50,21 @@ static void set_shift(const dfft_plan *p, PassArgs &X)
     X.ntiles = X.na * X.nb;
 }
 
+// n fresh launches of group g
+static std::vector<Launch> &group(Pipeline &pl, int g, size_t n)
+{
+    pl.groups[g].L.assign(n, Launch());
+    return pl.groups[g].L;
+}
+
+// (dfft_init may run again on the same plan: nothing of an earlier initialisation survives)
+static void clear(Pipeline &pl)
+{
+    for (auto &g : pl.groups) g.L.clear();
+    for (Chain *c : {&pl.fwd[0], &pl.fwd[1], &pl.fwd[2], &pl.inv[0], &pl.inv[1], &pl.inv[2], &pl.one_fwd, &pl.one_inv}) *c = Chain();
+    pl.single = false;
+}
+
 static void seg_push(SegTable &t, size_t start, size_t len, size_t base_elems)
 {
     int s = t.nseg++;
@@ -73,9 +88,9 @@ int build_pipeline(dfft_plan *p, Pipeline &pl)
     std::vector<std::vector<size_t>> xlq(P1), x0q(P1), klq(P1), k0q(P1);
     for (int q = 0; q < P1; q++) { split(p->xs[q], C, xlq[q], x0q[q]); split(p->yo[q], C, klq[q], k0q[q]); }
 
-    pl.fx = Launch();           // (initFFT may be called again on the same plan)
-    pl.fz.assign(C, Launch()); pl.fy.assign(C, Launch()); pl.ix.assign(C, Launch());
-    pl.iy.assign(C, Launch()); pl.iz.assign(C, Launch());
+    clear(pl);
+    auto &fz = group(pl, G_FZ, C), &fy = group(pl, G_FY, C), &ix = group(pl, G_IX, C), &iy = group(pl, G_IY, C), &iz = group(pl, G_IZ, C);
+    Launch &fx = group(pl, G_FX, 1)[0];
     pl.f1.assign(C, A2A()); pl.f2.assign(C, A2A()); pl.i2.assign(C, A2A()); pl.i1.assign(C, A2A());
 
     // ---------------- forward (mpicufft_pencil_opt1.cpp:1422-1519) ----------------
@@ -100,14 +115,14 @@ int build_pipeline(dfft_plan *p, Pipeline &pl)
             for (int c = 0; c < C; c++) {
                 size_t off = r2c_of[c];
                 for (int q2 = 0; q2 < q; q2++) off += xlq[q2][c] * yo * zs;
-                if (xlq[q][c]) seg_push(pl.fx.lseg, p->xstart[q] + x0q[q][c], xlq[q][c], off);
+                if (xlq[q][c]) seg_push(fx.lseg, p->xstart[q] + x0q[q][c], xlq[q][c], off);
             }
-        pl.fx.args = X;
+        fx.args = X;
     }
     for (int c = 0; c < C; c++) {
         const size_t S1c = x0[c] * Nzc * ys, R1c = x0[c] * zs * Ny, S2c = x0[c] * zs * Ny;
         {   // z pass chunk: natural lines -> send1 block (c,p) = [x][kz/TL][y][kz%TL], kz in zs[p]
-            Launch &L = pl.fz[c];
+            Launch &L = fz[c];
             L.args = base(xl[c], ys, LOAD_LINES, STORE_TILED_TRANSPOSE, 0);
             L.in_off = x0[c] * ys * zline_bytes;
             for (int q = 0; q < P2; q++) seg_push(L.sseg, p->zstart[q], p->zs[q], S1c + xl[c] * p->zstart[q] * ys);
@@ -122,7 +137,7 @@ int build_pipeline(dfft_plan *p, Pipeline &pl)
             }
         }
         {   // y pass chunk: lines along y from the P2 blocks -> send2 block (c,p) = [ky][kz/TL][x][kz%TL]
-            Launch &L = pl.fy[c];
+            Launch &L = fy[c];
             L.args = base(xl[c], zs, LOAD_TILED, STORE_TILED_SAME, 0);
             for (int q = 0; q < P2; q++) seg_push(L.lseg, p->ystart[q], p->ys[q], R1c + xl[c] * p->ystart[q] * zs);
             for (int q = 0; q < P1; q++) seg_push(L.sseg, p->yostart[q], p->yo[q], S2c + xl[c] * zs * p->yostart[q]);
@@ -147,7 +162,7 @@ int build_pipeline(dfft_plan *p, Pipeline &pl)
     for (int c = 0; c < C; c++) {
         const size_t S2i = k0[c] * zs * Nx;
         {   // x^-1 chunk (ky range): API layout point-major -> block (c,p) = [x][kz/TL][ky][kz%TL], x in xs[p]
-            Launch &L = pl.ix[c];
+            Launch &L = ix[c];
             L.args = base(kl[c], zs, LOAD_KMAJOR, STORE_TILED_SAME, 1);
             L.args.KS_in = (uint64_t)yo * zs;
             L.args.AS_in = zs;
@@ -185,7 +200,7 @@ int build_pipeline(dfft_plan *p, Pipeline &pl)
         const size_t S1i = x0[c] * Ny * zs, R1i = x0[c] * ys * Nzc;
         {   // y^-1 chunk (x range): lines along ky from the (peer, ky-chunk) blocks ->
             // block (c,p) = [x][y/TL][kz][y%TL], y in ys[p]
-            Launch &L = pl.iy[c];
+            Launch &L = iy[c];
             L.args = base(xl[c], zs, LOAD_TILED, STORE_TILED_TRANSPOSE, 1);
             for (int q = 0; q < P1; q++)
                 for (int c2 = 0; c2 < C; c2++) {
@@ -206,7 +221,7 @@ int build_pipeline(dfft_plan *p, Pipeline &pl)
             }
         }
         {   // z^-1 chunk: lines along kz from the P2 blocks -> natural [x][y][z]
-            Launch &L = pl.iz[c];
+            Launch &L = iz[c];
             L.args = base(xl[c], ys, LOAD_TILED, STORE_LINES, 1);
             L.args.xcd_swizzle = 1;       // measured +3 % on the natural-line stores
             for (int q = 0; q < P2; q++) seg_push(L.lseg, p->zstart[q], p->zs[q], R1i + xl[c] * ys * p->zstart[q]);
@@ -214,27 +229,54 @@ int build_pipeline(dfft_plan *p, Pipeline &pl)
         }
     }
     // ---------------- partial transforms (d = 1, 2) ----------------
-    pl.pz1 = Launch(); pl.qz1 = Launch();
-    pl.pz1.args = base(xs, ys, LOAD_LINES, STORE_LINES, 0);
-    pl.qz1.args = base(xs, ys, LOAD_LINES, STORE_LINES, 1);
-    pl.py2.assign(C, Launch()); pl.qy2.assign(C, Launch());
+    group(pl, G_PZ1, 1)[0].args = base(xs, ys, LOAD_LINES, STORE_LINES, 0);
+    group(pl, G_QZ1, 1)[0].args = base(xs, ys, LOAD_LINES, STORE_LINES, 1);
+    auto &py2 = group(pl, G_PY2, C), &qy2 = group(pl, G_QY2, C);
     for (int c = 0; c < C; c++) {
         const size_t R1c = x0[c] * zs * Ny, S1i = x0[c] * Ny * zs;
         {   // forward y pass chunk writing the reference's opt0 stage layout [xs][Ny][zs]
-            Launch &L = pl.py2[c];
+            Launch &L = py2[c];
             L.args = base(xl[c], zs, LOAD_TILED, STORE_KMAJOR, 0);
             for (int q = 0; q < P2; q++) seg_push(L.lseg, p->ystart[q], p->ys[q], R1c + xl[c] * p->ystart[q] * zs);
             L.args.KS_out = zs; L.args.AS_out = Ny * zs; L.args.xcd_swizzle = 1;
             L.out_off = e * x0[c] * Ny * zs;
         }
         {   // inverse y pass chunk reading [xs][Ny][zs]
-            Launch &L = pl.qy2[c];
+            Launch &L = qy2[c];
             L.args = base(xl[c], zs, LOAD_KMAJOR, STORE_TILED_TRANSPOSE, 1);
             L.args.KS_in = zs; L.args.AS_in = Ny * zs;
             L.in_off = e * x0[c] * Ny * zs;
             for (int q = 0; q < P2; q++) seg_push(L.sseg, p->ystart[q], p->ys[q], S1i + xl[c] * p->ystart[q] * zs);
         }
     }
+    // ---------------- execution chains ----------------
+    // Step: {group, form, src, dst, phase, exchange after each chunk, waits for the whole step before, launches per chunk, conjugated}.
+    // Work slices: one per exchange + 1, taken in order of use.
+    const int x1 = P2 > 1 ? 1 : 0, x2 = P1 > 1 ? 2 : 0;
+    const int zf = p->c2c ? FORM_FWD : FORM_REAL_Z1, zi = p->c2c ? FORM_INV : FORM_REAL_Z2;
+    {   // forward   z: in -> out   [ex1: out -> W0]   y: -> next   [ex2: -> next]   x: -> out.  Without exchange 1 (slab) y(c) only
+        // needs z(c): the two passes run interleaved, and the first chunk reaches the wire after one z and one y chunk
+        const int ysrc = P2 > 1 ? 0 : BUF_OUT, ydst = P2 > 1 ? 1 : 0, xsrc = P1 > 1 ? ydst + 1 : ydst;
+        pl.fwd[2].steps = {{G_FZ, zf, BUF_IN, BUF_OUT, 0, x1}, {G_FY, FORM_FWD, ysrc, ydst, 2, x2}, {G_FX, FORM_FWD, xsrc, BUF_OUT, 4, 0, true}};
+    }
+    {   // inverse   x^-1: in -> W0   [ex2: W0 -> W1]   y^-1: -> in   [ex1: in -> W0]   z^-1: -> out.  `in` is scratch once every x^-1
+        // chunk has read it; y^-1 needs complete ky lines (every chunk of exchange 2); without exchange 1 the chunks of y^-1 and z^-1
+        // need not coincide
+        const int ysrc = P1 > 1 ? 1 : 0, zsrc = P2 > 1 ? (P1 > 1 ? 0 : 1) : BUF_IN;      // (W0 is still read by y^-1 when there is no exchange 2)
+        pl.inv[2].steps = {{G_IX, FORM_INV, BUF_IN, 0, 0, x2}, {G_IY, FORM_INV, ysrc, BUF_IN, 2, x1, true}, {G_IZ, zi, zsrc, BUF_OUT, 4, 0, P2 == 1}};
+    }
+    pl.fwd[2].split = pl.inv[2].split = true;
+    // partial transforms: d = 1 stops after the z pass with the natural stage layout [xs][ys][Nzc]; d = 2 after the y pass with
+    // [xs][Ny][zs] (z contiguous)
+    pl.fwd[0].steps = {{G_PZ1, zf, BUF_IN, BUF_OUT}};
+    pl.inv[0].steps = {{G_QZ1, zi, BUF_IN, BUF_OUT}};
+    pl.fwd[1].steps = {{G_FZ, zf, BUF_IN, 0, -1, x1}, {G_PY2, FORM_FWD, x1, BUF_OUT, -1, 0, P2 == 1}};
+    pl.inv[1].steps = {{G_QY2, FORM_INV, BUF_IN, 0, -1, x1}, {G_IZ, zi, x1, BUF_OUT, -1, 0, P2 == 1}};
+    // single rank, complex: input and output are both natural [x][y][z], so the inverse may run the forward pass order with conjugation
+    // -- it avoids the strided read of the x-first order (the reference's fft3d branch is one cuFFT plan: the order is not observable)
+    if (p->nranks == 1 && p->c2c)
+        pl.one_inv.steps = {{G_FZ, FORM_FWD, BUF_IN, 0, 4, 0, false, 1, true}, {G_FY, FORM_FWD, 0, BUF_IN, 2, 0, true, 1, true},
+                            {G_FX, FORM_FWD, BUF_IN, BUF_OUT, 0, 0, true, 1, true}};
     return 0;
 }
 
@@ -263,17 +305,16 @@ int build_pipeline_zyx(dfft_plan *p, Pipeline &pl)
     std::vector<std::vector<size_t>> blk(C, std::vector<size_t>(P, 0));
     { size_t acc = 0; for (int c = 0; c < C; c++) for (int q = 0; q < P; q++) { blk[c][q] = acc; acc += xlq[q][c] * Ny * zs; } }
 
-    pl.fx = Launch(); pl.zix = Launch();
-    pl.fz.assign(C, Launch()); pl.iz.assign(C, Launch());
-    pl.zy.assign((size_t)C * P, Launch()); pl.ziy.assign((size_t)C * P, Launch());
+    clear(pl);
+    Launch &fx = group(pl, G_FX, 1)[0], &zix = group(pl, G_ZIX, 1)[0];
+    auto &fz = group(pl, G_FZ, C), &iz = group(pl, G_IZ, C), &zy = group(pl, G_ZY, (size_t)C * P), &ziy = group(pl, G_ZIY, (size_t)C * P);
     pl.f2.assign(C, A2A()); pl.i2.assign(C, A2A());
-    pl.fy.clear(); pl.ix.clear(); pl.iy.clear(); pl.f1.clear(); pl.i1.clear(); pl.py2.clear(); pl.qy2.clear();
-    pl.pz1 = Launch(); pl.qz1 = Launch();
+    pl.f1.clear(); pl.i1.clear();
 
     for (int c = 0; c < C; c++) {
         const size_t S1c = x0[c] * Nzc * Ny;     // send side: my x chunk, every kz
         {   // z pass chunk
-            Launch &L = pl.fz[c];
+            Launch &L = fz[c];
             L.args = base(xl[c], Ny, LOAD_LINES, STORE_TILED_TRANSPOSE, 0);
             L.in_off = x0[c] * Ny * zline_bytes;
             for (int q = 0; q < P; q++) seg_push(L.sseg, p->zstart[q], p->zs[q], S1c + xl[c] * p->zstart[q] * Ny);
@@ -288,7 +329,7 @@ int build_pipeline_zyx(dfft_plan *p, Pipeline &pl)
             }
         }
         for (int q = 0; q < P; q++) {   // y pass on the block received from q
-            Launch &L = pl.zy[(size_t)c * P + q];
+            Launch &L = zy[(size_t)c * P + q];
             L.args = base(xlq[q][c], zs, LOAD_TILED, STORE_TILED_SAME, 0);
             seg_push(L.lseg, 0, Ny, blk[c][q]);
             seg_push(L.sseg, 0, Ny, blk[c][q]);
@@ -299,14 +340,14 @@ int build_pipeline_zyx(dfft_plan *p, Pipeline &pl)
         PassArgs X = base(Ny, zs, LOAD_TILED, STORE_KMAJOR, 0);
         X.KS_out = (uint64_t)Ny * zs; X.AS_out = zs; X.xcd_swizzle = 1;
         set_shift(p, X);
-        pl.fx.args = X;
+        fx.args = X;
         for (int q = 0; q < P; q++)
             for (int c = 0; c < C; c++)
-                if (xlq[q][c]) seg_push(pl.fx.lseg, p->xstart[q] + x0q[q][c], xlq[q][c], blk[c][q]);
+                if (xlq[q][c]) seg_push(fx.lseg, p->xstart[q] + x0q[q][c], xlq[q][c], blk[c][q]);
     }
     // ---------------- inverse ----------------
     {   // x^-1: API layout -> blocks (c,q) = [x][kz/TL][ky][kz%TL]
-        Launch &L = pl.zix;
+        Launch &L = zix;
         L.args = base(Ny, zs, LOAD_KMAJOR, STORE_TILED_SAME, 1);
         L.args.KS_in = (uint64_t)Ny * zs; L.args.AS_in = zs;
         L.args.xcd_swizzle = 1; L.args.a_fastest = zs % TL == 0 ? 1 : 0;
@@ -318,7 +359,7 @@ int build_pipeline_zyx(dfft_plan *p, Pipeline &pl)
     for (int c = 0; c < C; c++) {
         const size_t R1i = x0[c] * Ny * Nzc;
         for (int q = 0; q < P; q++) {   // y^-1 on block (c,q) -> send block [x][y/TL][kz'][y%TL]
-            Launch &L = pl.ziy[(size_t)c * P + q];
+            Launch &L = ziy[(size_t)c * P + q];
             L.args = base(xlq[q][c], zs, LOAD_TILED, STORE_TILED_TRANSPOSE, 1);
             seg_push(L.lseg, 0, Ny, blk[c][q]);
             seg_push(L.sseg, 0, Ny, blk[c][q]);
@@ -333,13 +374,20 @@ int build_pipeline_zyx(dfft_plan *p, Pipeline &pl)
             }
         }
         {   // z^-1 chunk: lines along kz from the P blocks -> natural [x][y][z]
-            Launch &L = pl.iz[c];
+            Launch &L = iz[c];
             L.args = base(xl[c], Ny, LOAD_TILED, STORE_LINES, 1);
             L.args.xcd_swizzle = 1;
             for (int q = 0; q < P; q++) seg_push(L.lseg, p->zstart[q], p->zs[q], R1i + xl[c] * Ny * p->zstart[q]);
             L.out_off = x0[c] * Ny * zline_bytes;
         }
     }
+    // forward  z: in -> out   [ex: out -> W0]   y: W0 -> W1   x: W1 -> out
+    // inverse  x^-1: in -> W0   y^-1: W0 -> in   [ex: in -> W1]   z^-1: -> out      (Step: see build_pipeline)
+    const int x = P > 1 ? 2 : 0, ysrc = P > 1 ? 0 : BUF_OUT, ydst = P > 1 ? 1 : 0, zsrc = P > 1 ? 1 : BUF_IN;
+    pl.fwd[2].steps = {{G_FZ, p->c2c ? FORM_FWD : FORM_REAL_Z1, BUF_IN, BUF_OUT, 0, x}, {G_ZY, FORM_FWD, ysrc, ydst, 2, 0, false, P},
+                       {G_FX, FORM_FWD, ydst, BUF_OUT, 4, 0, true}};
+    pl.inv[2].steps = {{G_ZIX, FORM_INV, BUF_IN, 0, 0}, {G_ZIY, FORM_INV, 0, BUF_IN, 2, x, true, P},
+                       {G_IZ, p->c2c ? FORM_INV : FORM_REAL_Z2, zsrc, BUF_OUT, 4}};
     return 0;
 }
 
@@ -366,16 +414,17 @@ int build_pipeline_yzx(dfft_plan *p, Pipeline &pl)
     std::vector<std::vector<size_t>> blk(C, std::vector<size_t>(P, 0));
     { size_t acc = 0; for (int c = 0; c < C; c++) for (int q = 0; q < P; q++) { blk[c][q] = acc; acc += xlq[q][c] * yo * Nz; } }
 
-    pl.fx = Launch(); pl.yz = Launch(); pl.zix = Launch(); pl.pz1 = Launch(); pl.qz1 = Launch();
-    pl.fy.assign(C, Launch()); pl.f2.assign(C, A2A());
-    pl.fz.clear(); pl.iz.clear(); pl.ix.clear(); pl.iy.clear(); pl.zy.clear(); pl.ziy.clear();
-    pl.f1.clear(); pl.i1.clear(); pl.i2.clear(); pl.py2.clear(); pl.qy2.clear();
+    clear(pl);
+    Launch &fx = group(pl, G_FX, 1)[0], &yz = group(pl, G_YZ, 1)[0];
+    auto &fy = group(pl, G_FY, C);
+    pl.f2.assign(C, A2A());
+    pl.f1.clear(); pl.i1.clear(); pl.i2.clear();
     // in-place input lines: element (x, y, z) at (x*Ny + y)*Nz + z, in reals (R2C) or complex (C2C)
     const size_t in_elem = p->c2c ? e : e / 2;
     for (int c = 0; c < C; c++) {
         const size_t S1c = x0[c] * p->Nyc * Nz;
         {
-            Launch &L = pl.fy[c];
+            Launch &L = fy[c];
             L.args = base(xl[c], Nz, LOAD_KMAJOR, STORE_TILED_SAME);
             L.args.KS_in = Nz; L.args.AS_in = (uint64_t)Ny * Nz;
             L.args.LA = (uint32_t)xl[c];
@@ -393,19 +442,22 @@ int build_pipeline_yzx(dfft_plan *p, Pipeline &pl)
         }
     }
     {   // x pass: [ky][z/TL][x][z%TL] blocks -> [ky][kx/TL][z][kx%TL]
-        PassArgs X = base(yo, Nz, LOAD_TILED, STORE_TILED_TRANSPOSE);
-        pl.fx.args = X;
+        fx.args = base(yo, Nz, LOAD_TILED, STORE_TILED_TRANSPOSE);
         for (int q = 0; q < P; q++)
             for (int c = 0; c < C; c++)
-                if (xlq[q][c]) seg_push(pl.fx.lseg, p->xstart[q] + x0q[q][c], xlq[q][c], blk[c][q]);
-        seg_push(pl.fx.sseg, 0, Nx, 0);
+                if (xlq[q][c]) seg_push(fx.lseg, p->xstart[q] + x0q[q][c], xlq[q][c], blk[c][q]);
+        seg_push(fx.sseg, 0, Nx, 0);
     }
     {   // z pass: lines along z, lanes along kx -> out[(kx*yo + ky)*Nz + kz]
         PassArgs Z = base(yo, Nx, LOAD_TILED, STORE_LINES);
         Z.KS_out = (uint64_t)yo * Nz; Z.AS_out = Nz;
-        pl.yz.args = Z;
-        seg_push(pl.yz.lseg, 0, Nz, 0);
+        yz.args = Z;
+        seg_push(yz.lseg, 0, Nz, 0);
     }
+    // forward  y: in -> out   [ex: out -> W0]   x: W0 -> W1   z: W1 -> out; no inverse (as in the reference)   (Step: see build_pipeline)
+    const int x = P > 1 ? 2 : 0, xsrc = P > 1 ? 0 : BUF_OUT, xdst = P > 1 ? 1 : 0;
+    pl.fwd[2].steps = {{G_FY, p->c2c ? FORM_FWD : FORM_REAL_LINES, BUF_IN, BUF_OUT, 0, x}, {G_FX, FORM_FWD, xsrc, xdst, 2, 0, true},
+                       {G_YZ, FORM_FIXED, xdst, BUF_OUT, 4, 0, true}};
     return 0;
 }
 
@@ -424,6 +476,7 @@ int build_pipeline_single(dfft_plan *p, Pipeline &pl)
 {
     const int TL = p->TL;
     const size_t Nx = p->Nx, Ny = p->Ny, Nz = p->Nzc;
+    for (int g : {G_SZ, G_SX, G_SY}) pl.groups[g].L.clear();
     pl.single = false;
     // measured (profiles/r2_single_order.txt): the y-last pass gains (2048^3 fp32: 34.7 -> 25.1 ms) but the z pass loses
     // its contiguous 128 KiB read (8 lines from 8 x planes instead): 1024^3 fp64 38.0-38.8 vs 37.5 ms per step, fp32 21.4
@@ -432,14 +485,14 @@ int build_pipeline_single(dfft_plan *p, Pipeline &pl)
     if (p->nranks != 1 || !p->c2c || p->zyx || p->yzx || !order || p->opt.spectral) return 0;
     const size_t nb = (Nz + TL - 1) / TL;
     const size_t pad = (size_t)std::max(0, p->opt.single_pad) / p->esz;      // elements
-    pl.sz = Launch(); pl.sx = Launch(); pl.sy = Launch();
+    Launch &sz = group(pl, G_SZ, 1)[0], &sx = group(pl, G_SX, 1)[0], &sy = group(pl, G_SY, 1)[0];
     {   // z pass
         PassArgs Z = pass_args(TL, Ny, Nx, LOAD_LINES, STORE_TILED_TRANSPOSE, 0);
         Z.KS_in = (uint64_t)Ny * Nz;      // line stride: the 8 lines of a tile are adjacent in x
         Z.AS_in = Nz;                      // a = y
         Z.a_fastest = 1;                   // neighbouring workgroups read neighbouring (contiguous) lines
-        pl.sz.args = Z;
-        seg_push(pl.sz.sseg, 0, Nz, 0);
+        sz.args = Z;
+        seg_push(sz.sseg, 0, Nz, 0);
     }
     uint64_t SK, SB;
     if (p->opt.single_layout == 1) { SK = (uint64_t)TL * Ny + pad; SB = (uint64_t)Nx * SK + pad; pl.single_work_elems = nb * SB; }
@@ -448,9 +501,9 @@ int build_pipeline_single(dfft_plan *p, Pipeline &pl)
         PassArgs X = pass_args(TL, Ny, Nz, LOAD_TILED, STORE_TILED_SAME, 0);
         X.LA = (uint32_t)Ny; X.SK = SK; X.SB = SB;
         X.a_fastest = 1; X.xcd_swizzle = 1;      // neighbouring workgroups (y, y+1) write neighbouring 128-byte columns
-        pl.sx.args = X;
-        seg_push(pl.sx.lseg, 0, Nx, 0);
-        seg_push(pl.sx.sseg, 0, Nx, 0);
+        sx.args = X;
+        seg_push(sx.lseg, 0, Nx, 0);
+        seg_push(sx.sseg, 0, Nx, 0);
     }
     {   // y pass: L2 chunk (kx, kz tile) -> natural output
         PassArgs Y = pass_args(TL, Nx, Nz, LOAD_TILED, STORE_KMAJOR, 0);
@@ -460,9 +513,14 @@ int build_pipeline_single(dfft_plan *p, Pipeline &pl)
         if (!p->ax[1].bluestein && p->prec == DFFT_F64 && p->opt.shift != 0 && Y.AS_out % TL != 0 && Y.KS_out % TL == 0 && Y.LB >= (uint32_t)TL) {
             Y.shift = 1; Y.nb += 1; Y.ntiles = Y.na * Y.nb;      // odd row pitch: row-aligned tile windows (see set_shift)
         }
-        pl.sy.args = Y;
-        seg_push(pl.sy.lseg, 0, Ny, 0);
+        sy.args = Y;
+        seg_push(sy.lseg, 0, Ny, 0);
     }
+    // z: in -> out (L1)   x: out -> W0 (L2)   y: W0 -> out; the inverse runs the same launches with conjugation.  Phase slots follow the
+    // axis (0 z, 2 y, 4 x in forward naming; mirrored for the inverse naming) so that the per-phase report keeps its labels
+    pl.one_fwd.steps = {{G_SZ, FORM_FWD, BUF_IN, BUF_OUT, 0}, {G_SX, FORM_FWD, BUF_OUT, 0, 4, 0, true}, {G_SY, FORM_FWD, 0, BUF_OUT, 2, 0, true}};
+    pl.one_inv.steps = {{G_SZ, FORM_FWD, BUF_IN, BUF_OUT, 4, 0, false, 1, true}, {G_SX, FORM_FWD, BUF_OUT, 0, 0, 0, true, 1, true},
+                        {G_SY, FORM_FWD, 0, BUF_OUT, 2, 0, true, 1, true}};
     pl.single = true;
     return 0;
 }

@@ -61,27 +61,63 @@ struct A2A {
     std::vector<size_t> sc, sd, rc, rd;   // bytes, absolute displacements in the stage buffers
 };
 
+// The launch groups of a plan, one table (Pipeline::groups) under the names dfft_debug_get_pass takes.  G_FZ .. G_IZ are the
+// tunable passes 0 .. 5 (fz fy fx ix iy iz: options variant_* / order_*, dfft_get_pass_choices, dfft_tune_variants).
+enum GroupId {
+    G_FZ, G_FY, G_FX, G_IX, G_IY, G_IZ,   // default sequence (pencil, slab ZY_Then_X): forward z, y (per chunk), x; inverse x, y, z (per chunk)
+    G_PZ1, G_QZ1, G_PY2, G_QY2,           // partial transforms (reference: execR2C/C2R(out, in, d), src/pencil/mpicufft_pencil.cpp:1644-1839):
+                                          // d = 1 z pass natural -> natural [xs][ys][Nzc] and back; d = 2 y pass chunk -> [xs][Ny][zs] and back
+    G_ZY, G_ZIY, G_ZIX,                   // slab sequence Z_Then_YX (src/slab/z_then_yx/): y passes per (chunk, source peer) block, unchunked
+                                          // inverse x pass (z passes: fz / iz, forward x pass: fx)
+    G_YZ,                                 // Y_Then_ZX: final z pass (x pass = fx, y chunks = fy)
+    G_SZ, G_SX, G_SY,                     // single-rank complex plans, pass order z, x, y (build_pipeline_single): natural -> L1 -> L2 -> natural
+    NGROUPS
+};
+struct Group {
+    const char *name;
+    int axis;                  // 0 = z, 1 = y, 2 = x
+    std::vector<Launch> L;     // per chunk (zy / ziy: per chunk and peer); empty where the plan has no such launch
+};
+
+// One step of an execution chain: the launches of a group, chunk by chunk, with the exchange after each chunk (run_chain, dfft.hip).
+enum Buffer { BUF_IN = -2, BUF_OUT = -1 };     // and k >= 0: work-area slice k
+enum LineForm {
+    FORM_FWD,         // complex lines, kernel configuration vfwd[axis]
+    FORM_INV,         // complex lines, vinv[axis]
+    FORM_FIXED,       // complex lines, configuration 0
+    FORM_REAL_Z1,     // real z pass, mode 1 (R2C)
+    FORM_REAL_Z2,     // real z pass, mode 2 (C2R)
+    FORM_REAL_LINES   // real strided lines in, Hermitian half out (the y pass of a Y_Then_ZX R2C plan)
+};
+struct Step {
+    int group;             // GroupId (an index: dfft_init may rebuild the launches)
+    int form;              // LineForm
+    int src, dst;          // Buffer or work slice
+    int phase = -1;        // phase-timing slot of its launches (of its exchange: phase + 1); -1 none
+    int xchg = 0;          // 1 / 2: that exchange after each chunk, dst -> the next step's src (tables f1 / f2, or i1 / i2 in an inverse chain)
+    bool whole = false;    // chunk c waits for the whole step before it (else for chunk c of it only)
+    int per_chunk = 1;     // launches per chunk
+    bool conj = false;     // launched with conjugation (swap = 1)
+};
+struct Chain {
+    std::vector<Step> steps;
+    bool split = false;    // its chunks may alternate over two compute streams (option compute_streams)
+};
+
 struct Pipeline {
     int C = 1;
-    std::vector<Launch> fz, fy, ix, iy, iz;   // per chunk
-    Launch fx;                                 // forward x pass (needs complete lines)
-    // partial transforms (reference: execR2C/C2R(out, in, d), src/pencil/mpicufft_pencil.cpp:1644-1839)
-    Launch pz1, qz1;                           // d = 1: z pass natural -> natural [xs][ys][Nzc] and back
-    std::vector<Launch> py2, qy2;              // d = 2: y pass chunk -> [xs][Ny][zs] and back
-    // slab sequence Z_Then_YX (src/slab/z_then_yx/): y passes per (chunk, source peer) block and one
-    // unchunked inverse x pass; the exchange tables live in f2 / i2
-    std::vector<Launch> zy, ziy;
-    Launch zix;
-    Launch yz;                                 // Y_Then_ZX: final z pass (x pass = fx, y chunks = fy)
-    // single-rank complex plans, pass order z, x, y (build_pipeline_single): natural lines -> L1 -> L2 -> natural
-    Launch sz, sx, sy;
-    bool single = false;
+    Group groups[NGROUPS] = {{"fz", 0}, {"fy", 1}, {"fx", 2}, {"ix", 2}, {"iy", 1}, {"iz", 0}, {"pz1", 0}, {"qz1", 0}, {"py2", 1},
+                             {"qy2", 1}, {"zy", 1}, {"ziy", 1}, {"zix", 2}, {"yz", 0}, {"sz", 0}, {"sx", 2}, {"sy", 1}};
+    // execution chains: fwd[d - 1] / inv[d - 1] of dfft_exec_dim (d = 3: the whole transform); one_fwd / one_inv the alternatives of a
+    // single rank's complex plan (one_rank_alternative): the z, x, y order, or (one_inv alone) the forward launches with conjugation
+    Chain fwd[3], inv[3], one_fwd, one_inv;
+    bool single = false;                       // the z, x, y order is built
     size_t single_work_elems = 0;              // size of the padded L2 buffer
     std::vector<A2A> f1, f2, i2, i1;          // per chunk exchange tables
     std::vector<hipEvent_t> ev;               // reusable events
     hipStream_t comm_stream = nullptr;
     hipStream_t comm_stream2 = nullptr;       // second exchange of a pencil plan (disjoint links: may overlap the first)
-    hipStream_t compute_stream2 = nullptr;    // option compute_streams = 2: the odd pipeline chunks of a pass run here (enqueue_forward)
+    hipStream_t compute_stream2 = nullptr;    // option compute_streams = 2: the odd pipeline chunks of a pass run here (run_chain)
 };
 
 struct TimedSpan { hipEvent_t a = nullptr, b = nullptr; int phase = 0; bool used = false; };
@@ -171,4 +207,9 @@ int build_pipeline_yzx(dfft_plan *p, Pipeline &pl);
 int build_pipeline_single(dfft_plan *p, Pipeline &pl);
 // shared by dfft.hip and tune.hip
 int check_ready(dfft_plan *p);       // 0 when the plan is initialised and has its device state, else an error code
+// a single rank's complex plan may run its one-rank alternative chains (neither mirror_inverse nor an x-contiguous spectrum asks for
+// the mirrored order): read at every exec
+inline bool one_rank_alternative(const dfft_plan *p) { return p->nranks == 1 && p->c2c && !p->opt.mirror && !p->spectral_mirror; }
+// the launches of tunable pass k (fz fy fx ix iy iz) in the chain an exec would run now; nullptr where it runs none
+std::vector<Launch> *pass_launches(dfft_plan *p, int k);
 void graphs_clear(dfft_plan *p);     // drops the captured launch graphs (anything that changes the launches calls it)

@@ -83,13 +83,9 @@ static int tune_trial(dfft_plan *p, const void *in, void *o, void *b, float t[6]
 static int tune_variants(dfft_plan *p, const void *in, void *o, void *b, float &best, const std::function<void(float)> &note)
 {
     if (p->zyx || p->yzx) return 0;                 // the slab sequences keep their rules
-    Pipeline &pl = p->pl;
-    const bool shared = p->nranks == 1 && !p->opt.mirror && !p->spectral_mirror && p->c2c;      // a single rank's complex inverse runs the forward launches
-    const bool single = pl.single && shared;                            // ... in the z, x, y order (three launches)
-    std::vector<Launch> *vecs[6] = {&pl.fz, &pl.fy, nullptr, &pl.ix, &pl.iy, &pl.iz};
+    const bool shared = one_rank_alternative(p);      // a single rank's complex inverse runs the forward launches
     auto launches = [&](int k, const std::function<void(Launch &)> &f) {
-        if (single) { if (k < 3) f(k == 0 ? pl.sz : k == 1 ? pl.sy : pl.sx); return; }
-        if (k == 2) f(pl.fx); else for (auto &L : *vecs[k]) f(L);
+        if (std::vector<Launch> *v = pass_launches(p, k)) for (Launch &L : *v) f(L);
     };
     auto axis_of = [](int k) { return k < 3 ? k : 5 - k; };
     auto slot = [&](int k) -> int & { return k < 3 ? p->vfwd[k] : p->vinv[5 - k]; };

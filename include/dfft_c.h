@@ -318,6 +318,22 @@ int dfft_get_pass_choices(const dfft_plan *plan, int variant[6], int order[6], i
 /* name: "fz" "fy" "ix" "iy" "iz" "py2" "qy2" "zy" "ziy" (index = chunk, or chunk*P + peer for zy/ziy)
  * and "fx" "zix" "yz" "pz1" "qz1" "sz" "sx" "sy" (index 0; the last three: single-rank complex plans, order z, x, y).  Returns nonzero if the plan has no such launch. */
 int dfft_debug_get_pass(const dfft_plan *plan, const char *name, int index, dfft_pass_desc *desc);
+/* One step of the chain an exec would run now (dfft_debug_get_chain): the launches of a group, chunk by chunk, each chunk followed by
+ * the exchange, if any.  Chunk c runs the group's launches c*per_chunk .. (c+1)*per_chunk - 1. */
+typedef struct dfft_chain_step {
+    char group[8];          /* launch group, as dfft_debug_get_pass names it */
+    int32_t axis;           /* 0 z, 1 y, 2 x */
+    int32_t launches, per_chunk;
+    int32_t src, dst;       /* -2 the exec's input, -1 its output, k >= 0 slice k of the work area (dfft_domain_size bytes each) */
+    int32_t conj;           /* 1: launched with conjugation whatever the descriptor's swap says */
+    int32_t form;           /* 0 / 1 / 2 complex lines (forward / inverse / fixed kernel configuration), 3 real z lines in (R2C),
+                             * 4 real z lines out (C2R), 5 real strided lines in (R2C) */
+    int32_t exchange;       /* 0, or 1 / 2: that exchange after every chunk, dst -> the next step's src, with the tables
+                             * dfft_get_pipeline_tables reports for the exec's direction */
+} dfft_chain_step;
+/* the steps of the chain the next exec in `direction` of `dims` dimensions (1, 2: exec_dim's partial transforms; 3: the whole
+ * transform) would run, as options read at exec time choose it; *count receives the number of steps, at most `capacity` are written */
+int dfft_debug_get_chain(const dfft_plan *plan, int direction, int dims, dfft_chain_step *steps, int capacity, int *count);
 /* the per-point address table the kernels use for a segmented side of that launch (store = 0: load
  * side, 1: store side); entry i = {base[i], ln[i], aux[i]} as documented for SegEntry.  *count receives
  * the number of points; at most `capacity` entries are written. */

@@ -1,16 +1,16 @@
 """CPU model of the product's pass descriptors (test infrastructure, not a product path).
 
 The HIP kernels are addressed by `PassArgs` descriptors that the host builds per plan
-(distributedfft_amd/csrc/dfft.hip: build_pipeline, build_pipeline_zyx, build_pipeline_yzx).  This
-module reads those descriptors through the C ABI's introspection getters
+(distributedfft_amd/csrc/pipeline.hip: build_pipeline, build_pipeline_zyx, build_pipeline_yzx,
+build_pipeline_single).  This module reads those descriptors through the C ABI's introspection getters
 (dfft_debug_get_pass / dfft_debug_get_point_table, host only) and executes the documented address
 forms (fft_pass.hip.h: LoadKind / StoreKind, SegEntry) with numpy transforms, rank by rank, moving
 blocks between virtual ranks with the plan's own chunked exchange tables.  It checks what a GPU run
 cannot isolate: that every descriptor, segment table and per-point table of a plan describes a
 consistent data flow that ends in the reference's output layout -- without a GPU.
 
-Buffer routing mirrors enqueue_forward / enqueue_inverse / enqueue_*_zyx / enqueue_forward_yzx /
-enqueue_partial_* in dfft.hip and must be kept in step with them.
+The buffer routing is the library's own: the steps of the chain an exec would run
+(dfft_debug_get_chain, which run_chain in dfft.hip executes), replayed step by step.
 """
 import numpy as np
 
@@ -19,6 +19,7 @@ import distributedfft_amd as dfft
 LINES, TILED, KMAJOR = 0, 1, 2
 S_LINES, S_KMAJOR, S_SAME, S_TRANSPOSE = 0, 1, 2, 3
 ESZ = {"double": 16, "float": 8}      # bytes per complex element; a real element is half of it
+MODES = ["c2c", "c2c", "c2c", "r2c", "c2r", "r2c"]      # by line form of a chain step (dfft_chain_step::form)
 
 
 def _seg(starts, lens, bases, n):
@@ -127,8 +128,6 @@ class World:
         # a work-area slice may be larger than the domain (padded private layouts of the single-rank z, x, y order)
         self.wel = [max(pl.getDomainSize(), pl.getWorkSizeDevice() // max(1, (self.P1 > 1) + (self.P2 > 1) + 1)) // self.esz for pl in self.plans]
         self.single = self.P == 1 and self.plans[0].debugPass("sz") is not None
-        # option spectral_layout: the spectrum stays x-contiguous and a single rank's inverse runs the mirrored pass order (dfft_init)
-        self.spectral = bool((options or {}).get("spectral_layout", 0))
 
     def buffers(self, n=3):
         return [[np.full(self.wel[r], np.nan + 0j, dtype=np.complex128) for _ in range(n)] for r in range(self.P)]
@@ -149,158 +148,41 @@ class World:
                 n, e = rc[q] // self.esz, self.esz
                 recv[r][rd[q] // e: rd[q] // e + n] = send[peer][psd[me] // e: psd[me] // e + n]
 
-    # -- chains ------------------------------------------------------------------------------
-    def forward(self, ins, kind="default"):
-        Nx, Ny, Nz = self.shape
-        P1, P2, C, pls = self.P1, self.P2, self.C, self.plans
-        outs = [np.full(n, np.nan + 0j, dtype=np.complex128) for n in self.nel]
-        W = self.buffers()
-        zmode = "c2c" if self.c2c else "r2c"
-        if kind == "default" and self.single:
-            # one rank, complex: pass order z, x, y through L1 (out) and the padded L2 (work), enqueue_single
-            pl = pls[0]
-            Pass(pl, "sz").run(ins[0], outs[0], Nz)
-            Pass(pl, "sx").run(outs[0], W[0][0], Nx)
-            Pass(pl, "sy").run(W[0][0], outs[0], Ny)
-            return outs
-        if kind == "default":
-            ysrc = [W[r][0] if P2 > 1 else outs[r] for r in range(self.P)]
-            nxt = 1 if P2 > 1 else 0
-            ydst = [W[r][nxt] for r in range(self.P)]
-            xsrc = [W[r][nxt + 1] if P1 > 1 else ydst[r] for r in range(self.P)]
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    Pass(pl, "fz", c).run(ins[r], outs[r], Nz, zmode)
-                if P2 > 1:
-                    self.exchange(dfft.FORWARD, 1, c, outs, ysrc)
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    Pass(pl, "fy", c).run(ysrc[r], ydst[r], Ny)
-                if P1 > 1:
-                    self.exchange(dfft.FORWARD, 2, c, ydst, xsrc)
-            for r, pl in enumerate(pls):
-                Pass(pl, "fx").run(xsrc[r], outs[r], Nx)
-        elif kind == "zyx":
-            P = P1
-            ysrc = [W[r][0] if P > 1 else outs[r] for r in range(self.P)]
-            ydst = [W[r][1] if P > 1 else W[r][0] for r in range(self.P)]
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    Pass(pl, "fz", c).run(ins[r], outs[r], Nz, zmode)
-                if P > 1:
-                    self.exchange(dfft.FORWARD, 2, c, outs, ysrc)
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    for q in range(P):
-                        Pass(pl, "zy", c * P + q).run(ysrc[r], ydst[r], Ny)
-            for r, pl in enumerate(pls):
-                Pass(pl, "fx").run(ydst[r], outs[r], Nx)
-        elif kind == "yzx":
-            P = P1
-            xsrc = [W[r][0] if P > 1 else outs[r] for r in range(self.P)]
-            xdst = [W[r][1] if P > 1 else W[r][0] for r in range(self.P)]
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    Pass(pl, "fy", c).run(ins[r], outs[r], Ny, "c2c" if self.c2c else "r2c")
-                if P > 1:
-                    self.exchange(dfft.FORWARD, 2, c, outs, xsrc)
-            for r, pl in enumerate(pls):
-                Pass(pl, "fx").run(xsrc[r], xdst[r], Nx)
-                Pass(pl, "yz").run(xdst[r], outs[r], Nz)
-        return outs
-
-    def inverse(self, spec, kind="default"):
-        """spec: per-rank flat complex arrays in the output layout (destroyed); returns per-rank
-        flat arrays in the input layout (real for R2C plans)"""
-        Nx, Ny, Nz = self.shape
-        P1, P2, C, pls = self.P1, self.P2, self.C, self.plans
-        zmode = "c2c" if self.c2c else "c2r"
-        nin = [int(np.prod(pl.getInSize())) for pl in pls]
-        outs = [np.full(n, np.nan, dtype=np.complex128 if self.c2c else np.float64) for n in nin]
-        W = self.buffers(2)
-        if kind == "default" and self.single:
-            pl = pls[0]
-            for name, src, dst, N in (("sz", spec[0], outs[0], Nz), ("sx", outs[0], W[0][0], Nx), ("sy", W[0][0], outs[0], Ny)):
-                p = Pass(pl, name)
-                p.d.swap = 1
-                p.run(src, dst, N)
-            return outs
-        if kind == "default" and self.P == 1 and self.c2c and not self.spectral:
-            # single rank, complex: forward pass order with conjugation (enqueue_inverse fast path)
-            pl = pls[0]
-            for name, src, dst, N in (("fz", spec[0], W[0][0], Nz), ("fy", W[0][0], spec[0], Ny), ("fx", spec[0], outs[0], Nx)):
-                for c in range(C if name != "fx" else 1):
-                    p = Pass(pl, name, c)
-                    p.d.swap = 1
-                    p.run(src, dst, N)
-            return outs
-        if kind == "default":
-            xdst = [W[r][0] for r in range(self.P)]
-            ysrc = [W[r][1] if P1 > 1 else W[r][0] for r in range(self.P)]
-            zsrc = [(W[r][0] if P1 > 1 else W[r][1]) if P2 > 1 else spec[r] for r in range(self.P)]
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    Pass(pl, "ix", c).run(spec[r], xdst[r], Nx)
-                if P1 > 1:
-                    self.exchange(dfft.INVERSE, 2, c, xdst, ysrc)
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    Pass(pl, "iy", c).run(ysrc[r], spec[r], Ny)
-                if P2 > 1:
-                    self.exchange(dfft.INVERSE, 1, c, spec, zsrc)
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    Pass(pl, "iz", c).run(zsrc[r], outs[r], Nz, zmode)
-        elif kind == "zyx":
-            P = P1
-            zsrc = [W[r][1] if P > 1 else spec[r] for r in range(self.P)]
-            for r, pl in enumerate(pls):
-                Pass(pl, "zix").run(spec[r], W[r][0], Nx)
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    for q in range(P):
-                        Pass(pl, "ziy", c * P + q).run(W[r][0], spec[r], Ny)
-                if P > 1:
-                    self.exchange(dfft.INVERSE, 2, c, spec, zsrc)
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    Pass(pl, "iz", c).run(zsrc[r], outs[r], Nz, zmode)
-        return outs
-
-    def partial(self, ins, d, direction):
-        """execR2C/execC2R(out, in, d) for d = 1, 2 (enqueue_partial_*)"""
-        Nx, Ny, Nz = self.shape
-        P2, C, pls = self.P2, self.C, self.plans
-        fwd = direction == dfft.FORWARD
-        if fwd:
+    def run(self, direction, ins, dims=3):
+        """one exec of `dims` dimensions on every rank: the steps of the library's chain (dfft_debug_get_chain), each chunk of a step
+        on every rank, then the exchange that follows it.  ins: per-rank flat input arrays (destroyed where the chain uses them as
+        scratch); returns per-rank flat output arrays (complex after a forward exec, real after an R2C plan's inverse)"""
+        steps = self.plans[0].debugChain(direction, dims)
+        assert all(pl.debugChain(direction, dims) == steps for pl in self.plans[1:])
+        if direction == dfft.FORWARD:
             outs = [np.full(n, np.nan + 0j, dtype=np.complex128) for n in self.nel]
         else:
-            nin = [int(np.prod(pl.getInSize())) for pl in pls]
+            nin = [int(np.prod(pl.getInSize())) for pl in self.plans]
             outs = [np.full(n, np.nan, dtype=np.complex128 if self.c2c else np.float64) for n in nin]
-        zmode = "c2c" if self.c2c else ("r2c" if fwd else "c2r")
-        W = self.buffers(2)
-        if d == 1:
-            for r, pl in enumerate(pls):
-                Pass(pl, "pz1" if fwd else "qz1").run(ins[r], outs[r], Nz, zmode)
-            return outs
-        first = [W[r][0] for r in range(self.P)]
-        second = [W[r][1] if P2 > 1 else W[r][0] for r in range(self.P)]
-        if fwd:
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    Pass(pl, "fz", c).run(ins[r], first[r], Nz, zmode)
-                if P2 > 1:
-                    self.exchange(dfft.FORWARD, 1, c, first, second)
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    Pass(pl, "py2", c).run(second[r], outs[r], Ny)
-        else:
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    Pass(pl, "qy2", c).run(ins[r], first[r], Ny)
-                if P2 > 1:
-                    self.exchange(dfft.INVERSE, 1, c, first, second)
-            for c in range(C):
-                for r, pl in enumerate(pls):
-                    Pass(pl, "iz", c).run(second[r], outs[r], Nz, zmode)
+        W = self.buffers(1 + max([0] + [b for s in steps for b in (s["src"], s["dst"])]))
+        buf = lambda b: ins if b == -2 else outs if b == -1 else [W[r][b] for r in range(self.P)]
+        length = (self.shape[2], self.shape[1], self.shape[0])      # by axis: z, y, x
+        for i, s in enumerate(steps):
+            src, dst, per = buf(s["src"]), buf(s["dst"]), s["per_chunk"]
+            for c in range(s["launches"] // per):
+                for r, pl in enumerate(self.plans):
+                    for k in range(c * per, (c + 1) * per):
+                        p = Pass(pl, s["group"], k)
+                        if s["conj"]:
+                            p.d.swap = 1
+                        p.run(src[r], dst[r], length[s["axis"]], MODES[s["form"]])
+                if s["exchange"]:
+                    self.exchange(direction, s["exchange"], c, dst, buf(steps[i + 1]["src"]))
         return outs
+
+    def forward(self, ins):
+        return self.run(dfft.FORWARD, ins)
+
+    def inverse(self, spec):
+        """spec: per-rank flat complex arrays in the output layout (destroyed); returns per-rank
+        flat arrays in the input layout (real for R2C plans)"""
+        return self.run(dfft.INVERSE, spec)
+
+    def partial(self, ins, d, direction):
+        """execR2C/execC2R(out, in, d) for d = 1, 2"""
+        return self.run(direction, ins, d)

@@ -1,7 +1,7 @@
 """Every pass descriptor, segment table, per-point table and chunked exchange table of a plan,
 executed on the CPU by tests/layout_sim.py (numpy transforms + the documented address forms) and
 compared with the transform of the global array -- the GPU-free check of the plan wiring
-(build_pipeline / build_pipeline_zyx / build_pipeline_yzx in distributedfft_amd/csrc/dfft.hip).
+(build_pipeline / build_pipeline_zyx / build_pipeline_yzx in distributedfft_amd/csrc/pipeline.hip, routed by run_chain).
 The kernels themselves are covered by the -m gpu parity tests."""
 import numpy as np
 import pytest
@@ -98,9 +98,9 @@ def test_z_then_yx_descriptors(shape, P, c2c, chunks):
     w = World(dfft.MPIcuFFT_Slab_Z_Then_YX, shape, P, 1, c2c, chunks)
     g = global_field(shape, c2c)
     ins = local_inputs(w, g)
-    outs = w.forward(ins, "zyx")
+    outs = w.forward(ins)
     check_spectrum(w, outs, np.fft.fftn(g) if c2c else np.fft.rfftn(g))
-    check_round_trip(w, w.inverse(outs, "zyx"), ins)
+    check_round_trip(w, w.inverse(outs), ins)
 
 
 @pytest.mark.parametrize("chunks", [1, 2])
@@ -109,7 +109,7 @@ def test_z_then_yx_descriptors(shape, P, c2c, chunks):
 def test_y_then_zx_descriptors(shape, P, c2c, chunks):
     w = World(dfft.MPIcuFFT_Slab_Y_Then_ZX, shape, P, 1, c2c, chunks)
     g = global_field(shape, c2c)
-    outs = w.forward(local_inputs(w, g), "yzx")
+    outs = w.forward(local_inputs(w, g))
     want = np.fft.fftn(g)
     check_spectrum(w, outs, want if c2c else want[:, :shape[1] // 2 + 1, :])
 
@@ -155,22 +155,28 @@ def test_many_ranks_max_segments_and_fp32_tiles(cls, kind, shape, P1, P2, chunks
     w = World(cls, shape, P1, P2, c2c, chunks, precision=prec)
     if (P1, chunks) == (8, 4):
         assert w.C == 4       # 32 segments on the gathered axis: the MAXSEG limit of the kernels
+    # the sequence's own chain: Z_Then_YX runs its y passes per (chunk, peer) block
+    assert any(s["group"] == "zy" for s in w.plans[0].debugChain(dfft.FORWARD)) == (kind == "zyx")
     g = global_field(shape, c2c)
     ins = local_inputs(w, g)
-    outs = w.forward(ins, kind)
+    outs = w.forward(ins)
     check_spectrum(w, outs, np.fft.fftn(g) if c2c else np.fft.rfftn(g))
-    check_round_trip(w, w.inverse(outs, kind), ins)
+    check_round_trip(w, w.inverse(outs), ins)
 
 
 @pytest.mark.parametrize("prec", ["double", "float"])
 @pytest.mark.parametrize("options", [{"single_order": 1}, {"single_order": 1, "single_layout": 0}, {"single_order": 1, "single_pad": 0},
-                                     {"single_order": 1, "single_layout": 0, "single_pad": 384}, {"single_order": 0}, {}])
+                                     {"single_order": 1, "single_layout": 0, "single_pad": 384}, {"single_order": 0}, {},
+                                     {"mirror_inverse": 1}, {"single_order": 1, "mirror_inverse": 1}])
 @pytest.mark.parametrize("shape", [(16, 8, 32), (6, 5, 9), (24, 16, 20), (9, 16, 33)])
 def test_single_rank_complex_orders_and_padded_layouts(shape, options, prec):
     """one rank, complex: the z, x, y order (strided natural-line rows -> L1 -> padded L2 -> natural) in both L2 layouts
-    and with different row paddings, and the z, y, x order it replaces; forward == fftn, inverse round trip"""
+    and with different row paddings, and the z, y, x order it replaces; with mirror_inverse = 1 the multi-rank chains (pass order
+    x, y, z for the inverse) instead; forward == fftn, inverse round trip"""
     w = World(dfft.MPIcuFFT_Pencil_Opt1, shape, 1, 1, True, precision=prec, options=options)
     assert w.single == (options.get("single_order", 0) == 1)
+    inverse = [s["group"] for s in w.plans[0].debugChain(dfft.INVERSE)]
+    assert inverse == (["ix", "iy", "iz"] if options.get("mirror_inverse") else ["sz", "sx", "sy"] if w.single else ["fz", "fy", "fx"])
     if w.single:
         d = w.plans[0].debugPass("sx")
         esz = 16 if prec == "double" else 8
