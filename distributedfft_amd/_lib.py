@@ -36,7 +36,14 @@ class PassDesc(C.Structure):
 
 class ChainStep(C.Structure):
     _fields_ = [("group", C.c_char * 8), ("axis", C.c_int32), ("launches", C.c_int32), ("per_chunk", C.c_int32),
-                ("src", C.c_int32), ("dst", C.c_int32), ("conj", C.c_int32), ("form", C.c_int32), ("exchange", C.c_int32)]
+                ("src", C.c_int32), ("dst", C.c_int32), ("conj", C.c_int32), ("form", C.c_int32), ("exchange", C.c_int32),
+                ("split", C.c_int32)]
+
+
+class TraceOp(C.Structure):
+    """dfft_trace_op (include/dfft_c.h): one operation of an exec's stream and event schedule"""
+    _fields_ = [("kind", C.c_int32), ("stream", C.c_int32), ("event", C.c_int32), ("step", C.c_int32), ("chunk", C.c_int32),
+                ("launch", C.c_int32), ("src", C.c_int32), ("dst", C.c_int32), ("which", C.c_int32), ("scratch", C.c_int32)]
 
 
 # every symbol include/dfft_c.h declares: (name, restype, argtypes)
@@ -92,6 +99,7 @@ SYMBOLS = [
     ("dfft_get_pass_choices", _i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     ("dfft_debug_get_pass", _i, [_vp, C.c_char_p, _i, C.POINTER(PassDesc)]),
     ("dfft_debug_get_chain", _i, [_vp, _i, _i, C.POINTER(ChainStep), _i, C.POINTER(_i)]),
+    ("dfft_debug_trace_chain", _i, [_vp, _i, _i, C.POINTER(TraceOp), _i, C.POINTER(_i)]),
     ("dfft_debug_get_point_table", _i, [_vp, C.c_char_p, _i, _i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint32), _sz, _psz]),
     ("dfft_last_error", C.c_char_p, []),

@@ -477,6 +477,17 @@ class MPIcuFFT:
         check(lib().dfft_debug_get_chain(self._h, int(direction), int(dims), steps, n.value, C.byref(n)))
         return [{k: (getattr(s, k).decode() if k == "group" else getattr(s, k)) for k, _ in ChainStep._fields_} for s in steps]
 
+    def debugTrace(self, direction, dims=3):
+        """the stream and event schedule of an exec (dfft_debug_trace_chain): one dict per operation, keys as dfft_trace_op, in issue
+        order.  dims = 1, 2, 3: what the next exec would issue (host only); dims = 0: what the last exec in `direction` issued while
+        option trace was 1"""
+        from ._lib import TraceOp
+        n = C.c_int(0)
+        check(lib().dfft_debug_trace_chain(self._h, int(direction), int(dims), None, 0, C.byref(n)))
+        ops = (TraceOp * n.value)()
+        check(lib().dfft_debug_trace_chain(self._h, int(direction), int(dims), ops, n.value, C.byref(n)))
+        return [{k: getattr(o, k) for k, _ in TraceOp._fields_} for o in ops]
+
     def debugPointTable(self, name, index=0, store=False):
         """[(base, ln, aux)] per point of a segmented side (dfft_debug_get_point_table)"""
         n = C.c_size_t(0)

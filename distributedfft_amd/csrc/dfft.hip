@@ -383,13 +383,12 @@ static int launch(dfft_plan *p, const Launch &L, int form, int axis, bool conj, 
 // `ready`: an event recorded when the send data was complete (the producer kernel of this pipeline chunk), if the caller has one:
 // the relay orders its first hop after it instead of after everything on `stream` (comm.hpp)
 static int exchange_tables(dfft_plan *p, int which, const A2A &T, bool forward, const char *send, char *recv,
-                           hipStream_t stream, uint64_t tag = 0, hipEvent_t ready = nullptr)
+                           hipStream_t stream, int channel, uint64_t tag = 0, hipEvent_t ready = nullptr)
 {
     const bool first = which == 1;
     const std::vector<int> &grp = first ? p->group1 : p->group2;
     const int me = first ? p->pj : p->pi;
     if (!p->comm) return fail(ERR_STATE, "exchange without a communicator");
-    const int channel = (which == 2 && p->pl.comm_stream2 && stream == p->pl.comm_stream2) ? 1 : 0;
     // Two-hop relay (comm.hpp): a group that is a strict subset of the world leaves most xGMI links idle -- the column groups of
     // a 2 x 4 grid drive one link of seven.  Option "relay" of the communicator: bit 0 = exchange 2, bit 1 = exchange 1.
     if ((p->comm->relay & (first ? 2 : 1)) && grp.size() > 1 && (int)grp.size() < p->comm->nranks) {
@@ -416,7 +415,7 @@ static int exchange(dfft_plan *p, int which, bool forward, const void *send, voi
     T.sc = which == 1 ? p->sc1 : p->sc2; T.sd = which == 1 ? p->sd1 : p->sd2;
     T.rc = which == 1 ? p->rc1 : p->rc2; T.rd = which == 1 ? p->rd1 : p->rd2;
     // (the table is a temporary: name it by what it is -- exchange and direction)
-    return exchange_tables(p, which, T, forward, static_cast<const char *>(send), static_cast<char *>(recv), p->stream,
+    return exchange_tables(p, which, T, forward, static_cast<const char *>(send), static_cast<char *>(recv), p->stream, 0,
                            16 + 2 * (uint64_t)which + (forward ? 1 : 0));
 }
 
@@ -476,80 +475,179 @@ std::vector<Launch> *pass_launches(dfft_plan *p, int k)
     return g < 0 ? nullptr : &p->pl.groups[g].L;
 }
 
-// Runs one execution chain (Pipeline::fwd / inv / one_fwd / one_inv).  The streams and events follow from its steps:
-//  - chunk c of a step runs on compute stream c mod 2 where the chain may split and the plan uses two compute streams (never while
-//    two-level passes share their scratch); every other launch runs on the plan's stream
-//  - the exchange after chunk c runs on the communication stream of that exchange (2: comm_stream2 where the transport has concurrent
+// true where run_graphed replays (or is about to capture) the launches of an exec as one hipGraph: it captures the plan's stream alone
+static bool graph_replay(const dfft_plan *p) { return p->opt.graph && p->nranks == 1 && !p->timing && (p->stream || !p->stream_user); }
+
+// a launch of this line form on this axis goes through the plan's shared level scratch (two-level and long-Bluestein lines: launch())
+static bool through_level_scratch(const dfft_plan *p, int form, int axis)
+{
+    const Axis &ax = p->ax[axis];
+    const bool real = form == FORM_REAL_Z1 || form == FORM_REAL_Z2 || form == FORM_REAL_LINES;
+    if (real && (form == FORM_REAL_LINES ? p->yreal_native : p->zreal_native)) return false;      // packed real kernels
+    return ax.bluestein && (ax.longb || ax.two);
+}
+
+// The streams of an exec, as dfft_trace_op::stream numbers them, and which of them beside the plan's own an exec of chain `ch` uses:
+// a predicate of the plan (options, chain, transport) shared by run_chain, the dry trace and the stream creation
+enum { S_MAIN = 0, S_COMPUTE2 = 1, S_COMM = 2, S_COMM2 = 3 };
+struct StreamUse { bool compute2, comm, comm2; };
+static StreamUse streams_of(const dfft_plan *p, const Chain &ch)
+{
+    StreamUse u{};
+    bool ex2 = false;
+    for (const Step &s : ch.steps) ex2 = ex2 || s.xchg == 2;
+    // two compute streams: never while two-level passes share one scratch, never under a graph capture of the plan's stream
+    u.compute2 = ch.split && compute_streams_of(p) > 1 && !p->lv_bytes && !graph_replay(p);
+    u.comm = p->comm && p->nranks > 1 && ch.steps.size() > 1;
+    u.comm2 = u.comm && ex2 && p->P1 > 1 && p->P2 > 1 && p->comm->concurrent_channels();
+    return u;
+}
+
+// ---- the leaf actions of run_chain go through a sink: HipSink issues them (and lists them under option trace), DrySink only lists
+// them (dfft_debug_trace_chain).  Both build their records with the same functions.
+static dfft_trace_op trace_launch(const dfft_plan *p, const std::vector<Step> &st, int step, int chunk, int k, int stream)
+{
+    const Step &t = st[(size_t)step];
+    const Group &g = p->pl.groups[t.group];
+    const int scratch = g.L[(size_t)k].args.ntiles != 0 && through_level_scratch(p, t.form, g.axis);
+    return {0, stream, -1, step, chunk, k, t.src, t.dst, 0, scratch};
+}
+static dfft_trace_op trace_exchange(const std::vector<Step> &st, int step, int chunk, int stream)
+{
+    const Step &t = st[(size_t)step];
+    return {1, stream, -1, step, chunk, -1, t.dst, st[(size_t)step + 1].src, t.xchg, 0};
+}
+static dfft_trace_op trace_sync(int kind, int stream, int event) { return {kind, stream, event, -1, -1, -1, -1, -1, 0, 0}; }
+
+struct DrySink {
+    const dfft_plan *p;
+    const std::vector<Step> &st;
+    std::vector<dfft_trace_op> &ops;
+    int kernel(int step, int chunk, int k, int s) { ops.push_back(trace_launch(p, st, step, chunk, k, s)); return 0; }
+    int xchg(int step, int chunk, int s, int /*ready*/) { ops.push_back(trace_exchange(st, step, chunk, s)); return 0; }
+    int record(int s, int e) { ops.push_back(trace_sync(2, s, e)); return 0; }
+    int wait(int e, int s) { ops.push_back(trace_sync(3, s, e)); return 0; }
+    int begin(int, int) { return 0; }
+    int end(int) { return 0; }
+};
+
+struct HipSink {
+    dfft_plan *p;
+    const std::vector<Step> &st;
+    int direction;
+    void *out;
+    const void *in;
+    std::vector<dfft_trace_op> *log;      // option trace, else nullptr
+    hipStream_t S[4];
+    // the streams the exec uses; one that does not exist yet is created here
+    int open(const StreamUse &use)
+    {
+        Pipeline &pl = p->pl;
+        if (use.compute2 && !pl.compute_stream2) HIP_TRY(hipStreamCreateWithFlags(&pl.compute_stream2, hipStreamNonBlocking));
+        if (use.comm && !pl.comm_stream) HIP_TRY(hipStreamCreateWithFlags(&pl.comm_stream, hipStreamNonBlocking));
+        if (use.comm2 && !pl.comm_stream2) HIP_TRY(hipStreamCreateWithFlags(&pl.comm_stream2, hipStreamNonBlocking));
+        S[S_MAIN] = p->stream; S[S_COMPUTE2] = pl.compute_stream2; S[S_COMM] = pl.comm_stream; S[S_COMM2] = pl.comm_stream2;
+        return 0;
+    }
+    char *buf(int b) const
+    {
+        return b == BUF_IN ? const_cast<char *>(static_cast<const char *>(in)) : b == BUF_OUT ? static_cast<char *>(out)
+                                                                               : static_cast<char *>(p->work_d) + (size_t)b * p->domainsize;
+    }
+    int kernel(int step, int chunk, int k, int s)
+    {
+        const Step &t = st[(size_t)step];
+        const Group &g = p->pl.groups[t.group];
+        if (log) log->push_back(trace_launch(p, st, step, chunk, k, s));
+        return launch(p, g.L[(size_t)k], t.form, g.axis, t.conj, buf(t.src), buf(t.dst), S[s]);
+    }
+    int xchg(int step, int chunk, int s, int ready)
+    {
+        const Step &t = st[(size_t)step];
+        const Pipeline &pl = p->pl;
+        const std::vector<A2A> &T = direction == DFFT_INVERSE ? (t.xchg == 1 ? pl.i1 : pl.i2) : (t.xchg == 1 ? pl.f1 : pl.f2);
+        if (log) log->push_back(trace_exchange(st, step, chunk, s));
+        return exchange_tables(p, t.xchg, T[(size_t)chunk], true, buf(t.dst), buf(st[(size_t)step + 1].src), S[s], s == S_COMM2 ? 1 : 0, 0,
+                               pl.ev[(size_t)ready]);      // (tables in send / receive order)
+    }
+    int record(int s, int e)
+    {
+        hipEvent_t ev = pipe_event(p, (size_t)e);
+        if (!ev) return fail(1, "hipEventCreate failed");
+        if (log) log->push_back(trace_sync(2, s, e));
+        HIP_TRY(hipEventRecord(ev, S[s]));
+        return 0;
+    }
+    int wait(int e, int s)
+    {
+        if (log) log->push_back(trace_sync(3, s, e));
+        HIP_TRY(hipStreamWaitEvent(S[s], p->pl.ev[(size_t)e], 0));
+        return 0;
+    }
+    int begin(int phase, int s) { return span_begin(p, phase, S[s]); }
+    int end(int s) { return span_end(p, S[s]); }
+};
+
+// The schedule of one execution chain (Pipeline::fwd / inv / one_fwd / one_inv): the one place that decides which stream a launch or
+// an exchange takes and which events order them.  Streams and events are numbers here (dfft_trace_op); the sink acts on them.
+//  - chunk c of a step runs on compute stream c mod 2 where the chain may split and the plan uses two compute streams (streams_of:
+//    never while two-level passes share their scratch); every other launch runs on the plan's stream
+//  - the exchange after chunk c runs on the communication stream of that exchange (2: the second one where the transport has concurrent
 //    channels) behind an event recorded after the chunk (the relay's `ready`: comm.hpp), and records the event its consumer waits for
 //  - chunk c of a step waits for the exchange of chunk c before it, or -- `whole` -- for all of the step before: the last exchange
 //    chunk (the communication stream is in order) and the other compute stream; steps that depend chunk by chunk without an exchange
 //    between them run interleaved, chunk c of the second right behind chunk c of the first
 //  - the communication streams start after the caller's prior work (entry fence), the caller's stream ends after the second compute stream
-static int run_chain(dfft_plan *p, int direction, int dims, void *out, const void *in)
+template <typename Sink> static int schedule_chain(const dfft_plan *p, const Chain &ch, const StreamUse &use, Sink &sk)
 {
-    const Chain &ch = chain_of(p, direction, dims);
     const std::vector<Step> &st = ch.steps;
-    if (st.empty()) return fail(ERR_UNSUPPORTED, "the Y_Then_ZX sequence is forward only (as in the reference)");
-    Pipeline &pl = p->pl;
-    auto buf = [&](int b) {
-        return b == BUF_IN ? const_cast<char *>(static_cast<const char *>(in)) : b == BUF_OUT ? static_cast<char *>(out)
-                                                                               : static_cast<char *>(p->work_d) + (size_t)b * p->domainsize;
-    };
-    hipStream_t Sc = p->stream, Sm = pl.comm_stream;
-    hipStream_t Sm2 = (pl.comm_stream2 && p->comm && p->comm->concurrent_channels()) ? pl.comm_stream2 : Sm;
-    hipStream_t Sc2 = (ch.split && compute_streams_of(p) > 1 && !p->lv_bytes) ? pl.compute_stream2 : nullptr;     // (two-level passes share one scratch)
-    auto SC = [&](int c) { return (Sc2 && (c & 1)) ? Sc2 : Sc; };
-    p->nspans = 0; p->last_dir = direction == DFFT_INVERSE ? DFFT_INVERSE : DFFT_FORWARD;
-    size_t nev = 0;     // events of this exec, in order of use
-    auto record = [&](hipStream_t s, hipEvent_t &e) -> int {
-        e = pipe_event(p, nev++);
-        if (!e) return fail(1, "hipEventCreate failed");
-        HIP_TRY(hipEventRecord(e, s));
-        return 0;
-    };
-    auto wait = [&](hipEvent_t e, hipStream_t s) -> int { HIP_TRY(hipStreamWaitEvent(s, e, 0)); return 0; };
-    auto join = [&](hipStream_t from, hipStream_t to) -> int { hipEvent_t e; TRY(record(from, e)); return wait(e, to); };
-    const bool comm = p->comm && p->nranks > 1 && st.size() > 1;
+    const Pipeline &pl = p->pl;
+    const int Sc = S_MAIN, Sc2 = S_COMPUTE2, Sm = S_COMM, Sm2 = use.comm2 ? S_COMM2 : S_COMM;
+    const bool two = use.compute2;
+    auto SC = [&](int c) { return (two && (c & 1)) ? Sc2 : Sc; };
+    int nev = 0;     // events of this exec, in order of use
+    auto record = [&](int s, int &e) -> int { e = nev++; return sk.record(s, e); };
+    auto wait = [&](int e, int s) -> int { return sk.wait(e, s); };
+    auto join = [&](int from, int to) -> int { int e; TRY(record(from, e)); return wait(e, to); };
+    const bool comm = use.comm;
     bool ex2 = false;
     for (const Step &s : st) ex2 = ex2 || s.xchg == 2;
-    hipEvent_t fence = nullptr;
-    if (comm || Sc2) TRY(record(Sc, fence));
+    int fence = -1;
+    if (comm || two) TRY(record(Sc, fence));
     if (comm) { TRY(wait(fence, Sm)); if (ex2 && Sm2 != Sm) TRY(wait(fence, Sm2)); }
-    if (Sc2) TRY(wait(fence, Sc2));
-    hipEvent_t xdone[MAXSEG];     // exchange of chunk c of the step before is complete
+    if (two) TRY(wait(fence, Sc2));
+    int xdone[MAXSEG];            // exchange of chunk c of the step before is complete
     int xprev = 0, xn = 0;        // ... which exchange that was (0: none), after how many chunks
     for (size_t s0 = 0, s1; s0 < st.size(); s0 = s1) {
         for (s1 = s0 + 1; s1 < st.size() && !st[s1].whole && !st[s1 - 1].xchg; s1++) {}      // steps [s0, s1) run interleaved
         const Step &first = st[s0];
         const int nchunk = (int)(pl.groups[first.group].L.size() / first.per_chunk);
-        const bool spread = Sc2 && nchunk > 1;      // on both compute streams
+        const bool spread = two && nchunk > 1;      // on both compute streams
         if (first.whole) {
             if (spread) {      // both compute streams have finished what they were given so far
-                hipEvent_t a, b;
+                int a, b;
                 TRY(record(Sc2, a)); TRY(record(Sc, b)); TRY(wait(a, Sc)); TRY(wait(b, Sc2));
             }
             if (xprev) { TRY(wait(xdone[xn - 1], Sc)); if (spread) TRY(wait(xdone[xn - 1], Sc2)); }
-            if (Sc2 && !spread) TRY(join(Sc2, Sc));
+            if (two && !spread) TRY(join(Sc2, Sc));
         }
         for (int c = 0; c < nchunk; c++) {
-            hipStream_t S = SC(c);
+            const int S = SC(c);
             if (!first.whole && xprev) TRY(wait(xdone[c], S));
             for (size_t i = s0; i < s1; i++) {
                 const Step &t = st[i];
-                const Group &g = pl.groups[t.group];
-                if (t.phase >= 0) TRY(span_begin(p, t.phase, S));
-                for (int k = c * t.per_chunk; k < (c + 1) * t.per_chunk; k++) TRY(launch(p, g.L[k], t.form, g.axis, t.conj, buf(t.src), buf(t.dst), S));
-                if (t.phase >= 0) TRY(span_end(p, S));
+                if (t.phase >= 0) TRY(sk.begin(t.phase, S));
+                for (int k = c * t.per_chunk; k < (c + 1) * t.per_chunk; k++) TRY(sk.kernel((int)i, c, k, S));
+                if (t.phase >= 0) TRY(sk.end(S));
             }
             const Step &t = st[s1 - 1];
             if (t.xchg) {
-                const std::vector<A2A> &T = direction == DFFT_INVERSE ? (t.xchg == 1 ? pl.i1 : pl.i2) : (t.xchg == 1 ? pl.f1 : pl.f2);
-                hipStream_t Sx = t.xchg == 1 ? Sm : Sm2;
-                hipEvent_t ready;
+                const int Sx = t.xchg == 1 ? Sm : Sm2;
+                int ready;
                 TRY(record(S, ready)); TRY(wait(ready, Sx));
-                if (t.phase >= 0) TRY(span_begin(p, t.phase + 1, Sx));
-                TRY(exchange_tables(p, t.xchg, T[c], true, buf(t.dst), buf(st[s1].src), Sx, 0, ready));      // (tables in send / receive order)
-                if (t.phase >= 0) TRY(span_end(p, Sx));
+                if (t.phase >= 0) TRY(sk.begin(t.phase + 1, Sx));
+                TRY(sk.xchg((int)s1 - 1, c, Sx, ready));
+                if (t.phase >= 0) TRY(sk.end(Sx));
                 TRY(record(Sx, xdone[c]));
             }
         }
@@ -557,6 +655,20 @@ static int run_chain(dfft_plan *p, int direction, int dims, void *out, const voi
         if (s1 == st.size() && spread) TRY(join(Sc2, Sc));      // the caller's stream follows the odd chunks
     }
     return 0;
+}
+
+// Runs one execution chain: schedule_chain through the sink that issues HIP calls
+static int run_chain(dfft_plan *p, int direction, int dims, void *out, const void *in)
+{
+    const Chain &ch = chain_of(p, direction, dims);
+    if (ch.steps.empty()) return fail(ERR_UNSUPPORTED, "the Y_Then_ZX sequence is forward only (as in the reference)");
+    const StreamUse use = streams_of(p, ch);
+    p->nspans = 0; p->last_dir = direction == DFFT_INVERSE ? DFFT_INVERSE : DFFT_FORWARD;
+    std::vector<dfft_trace_op> *log = nullptr;
+    if (p->opt.trace) { log = &p->trace_log[direction == DFFT_INVERSE ? 1 : 0]; log->clear(); }
+    HipSink sk{p, ch.steps, direction, out, in, log, {}};
+    TRY(sk.open(use));
+    return schedule_chain(p, ch, use, sk);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -574,7 +686,7 @@ void graphs_clear(dfft_plan *p)
 }
 template <typename F> static int run_graphed(dfft_plan *p, int kind, const void *in, void *out, F &&enqueue)
 {
-    if (!p->opt.graph || p->nranks != 1 || p->timing || !p->stream) return enqueue();
+    if (!graph_replay(p) || !p->stream) return enqueue();
     dfft_plan::GraphEntry *e = nullptr;
     for (auto &g : p->graphs) if (g.kind == kind && g.in == in && g.out == out) { e = &g; break; }
     if (e && e->exec) { HIP_TRY(hipGraphLaunch(e->exec, p->stream)); return 0; }
@@ -771,6 +883,7 @@ static int *option_slot(Options &o, const std::string &k)
     if (k == "graph") return &o.graph;
     if (k == "spectral_layout") return &o.spectral;
     if (k == "compute_streams") return &o.compute_streams;
+    if (k == "trace") return &o.trace;
     for (int i = 0; i < 6; i++) {
         if (k == std::string("variant_") + kPassNames[i]) return &o.variant[i];
         if (k == std::string("order_") + kPassNames[i]) return &o.order[i];
@@ -1092,11 +1205,11 @@ static int ensure_device_state(dfft_plan *p)
         HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
         p->stream_owned = true;
     }
-    if (p->comm && !p->pl.comm_stream) HIP_TRY(hipStreamCreateWithFlags(&p->pl.comm_stream, hipStreamNonBlocking));
-    if (p->comm && p->P1 > 1 && p->P2 > 1 && !p->pl.comm_stream2)
-        HIP_TRY(hipStreamCreateWithFlags(&p->pl.comm_stream2, hipStreamNonBlocking));
-    if (compute_streams_of(p) > 1 && !p->pl.compute_stream2)
-        HIP_TRY(hipStreamCreateWithFlags(&p->pl.compute_stream2, hipStreamNonBlocking));
+    // the streams the whole transform needs as the options stand (an exec creates what it needs beyond them: HipSink::open)
+    for (const Chain *ch : {&chain_of(p, DFFT_FORWARD, 3), &chain_of(p, DFFT_INVERSE, 3)}) {
+        HipSink sk{p, ch->steps, DFFT_FORWARD, nullptr, nullptr, nullptr, {}};
+        TRY(sk.open(streams_of(p, *ch)));
+    }
     return 0;
 }
 
@@ -1326,7 +1439,8 @@ int dfft_debug_get_chain(const dfft_plan *p, int direction, int dims, dfft_chain
 {
     if (!p || !p->initialized) return fail(ERR_STATE, "plan not initialised");
     if (dims < 1 || dims > 3 || (direction != DFFT_FORWARD && direction != DFFT_INVERSE)) return fail(ERR_ARG, "bad direction or dims");
-    const std::vector<Step> &st = chain_of(p, direction, dims).steps;
+    const Chain &ch = chain_of(p, direction, dims);
+    const std::vector<Step> &st = ch.steps;
     if (count) *count = (int)st.size();
     for (size_t i = 0; i < st.size() && (int)i < capacity; i++) {
         const Step &s = st[i];
@@ -1335,8 +1449,24 @@ int dfft_debug_get_chain(const dfft_plan *p, int direction, int dims, dfft_chain
         memset(&d, 0, sizeof(d));
         strncpy(d.group, g.name, sizeof(d.group) - 1);
         d.axis = g.axis; d.launches = (int32_t)g.L.size(); d.per_chunk = s.per_chunk;
-        d.src = s.src; d.dst = s.dst; d.conj = s.conj; d.form = s.form; d.exchange = s.xchg;
+        d.src = s.src; d.dst = s.dst; d.conj = s.conj; d.form = s.form; d.exchange = s.xchg; d.split = ch.split;
     }
+    return 0;
+}
+
+int dfft_debug_trace_chain(const dfft_plan *p, int direction, int dims, dfft_trace_op *ops, int capacity, int *count)
+{
+    if (!p || !p->initialized) return fail(ERR_STATE, "plan not initialised");
+    if (dims < 0 || dims > 3 || (direction != DFFT_FORWARD && direction != DFFT_INVERSE)) return fail(ERR_ARG, "bad direction or dims");
+    std::vector<dfft_trace_op> dry;
+    if (dims > 0) {
+        const Chain &ch = chain_of(p, direction, dims);
+        DrySink sk{p, ch.steps, dry};
+        TRY(schedule_chain(p, ch, streams_of(p, ch), sk));
+    }
+    const std::vector<dfft_trace_op> &v = dims > 0 ? dry : p->trace_log[direction == DFFT_INVERSE ? 1 : 0];
+    if (count) *count = (int)v.size();
+    for (size_t i = 0; i < v.size() && (int)i < capacity; i++) ops[i] = v[i];
     return 0;
 }
 

@@ -115,6 +115,8 @@ struct Pipeline {
     size_t single_work_elems = 0;              // size of the padded L2 buffer
     std::vector<A2A> f1, f2, i2, i1;          // per chunk exchange tables
     std::vector<hipEvent_t> ev;               // reusable events
+    // streams beside the plan's own.  Which of them an exec uses is decided by streams_of (dfft.hip), never by whether a handle exists:
+    // what that predicate asks for and is not there yet is created when an exec first needs it
     hipStream_t comm_stream = nullptr;
     hipStream_t comm_stream2 = nullptr;       // second exchange of a pencil plan (disjoint links: may overlap the first)
     hipStream_t compute_stream2 = nullptr;    // option compute_streams = 2: the odd pipeline chunks of a pass run here (run_chain)
@@ -152,6 +154,7 @@ struct Options {
                              // the chunks queue up behind each other on one stream).  -1 = by measurement
                              // (profiles/r6_compute_streams.txt): two streams from three chunks per pass on (rank 0 of 2x4, 1024^3
                              // fp64: 4 chunks 4.89 -> 4.78 ms, 8 chunks 5.31 -> 4.90; at two chunks there is nothing to gain), 1 = one
+    int trace = 0;           // debug: 1 = every exec keeps the list of what it issued (dfft_debug_trace_chain with dims = 0)
     int order[6] = {-1, -1, -1, -1, -1, -1};     // workgroup->tile order per pass: fz fy fx ix iy iz; a_fastest + 2*xcd_swizzle
     int variant[6] = {-1, -1, -1, -1, -1, -1};   // kernel configuration per pass, same order (-1 = the plan's choice)
 };
@@ -194,6 +197,7 @@ struct dfft_plan {
     std::vector<TimedSpan> spans;
     size_t nspans = 0;
     int last_dir = -1;
+    std::vector<dfft_trace_op> trace_log[2];   // option trace: what the last forward / inverse exec issued
     // hipGraph replay of single-rank execs (launch-bound small grids): one instantiated graph per (operation, in, out)
     struct GraphEntry { int kind; const void *in; void *out; int uses; hipGraphExec_t exec; };
     std::vector<GraphEntry> graphs;

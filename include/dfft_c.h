@@ -193,6 +193,15 @@ int dfft_get_pipeline_chunks(const dfft_plan *plan);
  *   "graph"            1: a single-rank plan replays the kernel launches of an exec as one hipGraph from the second call
  *                      with the same (operation, in, out) on; 0 (default): plain launches -- measured 6-8 us faster per
  *                      exec on ROCm 7.2 (profiles/r2_graph_latency.txt)
+ *                      Such a plan runs on its own stream alone (no second compute stream): only that stream is captured.
+ *   "compute_streams"  2: the pipeline chunks of a pass alternate over two compute streams (chunk c on stream c mod 2), so that the
+ *                      drain of one chunk overlaps the ramp of the next; 1: one stream; -1 (default): two from three chunks per pass
+ *                      on.  Read at every exec: it takes effect at the NEXT EXEC, also when it is set after dfft_init and after
+ *                      dfft_set_work_area (the second stream is created by the first exec that needs it).  Never two streams while
+ *                      two-level or long-Bluestein passes share the plan's level scratch, under "graph", or at a pipeline depth of 1;
+ *                      dfft_debug_trace_chain shows what the next exec does.
+ *   "trace"            debug, 0 (default) | 1: every exec keeps the list of the launches, exchanges, event records and stream waits
+ *                      it issued, readable through dfft_debug_trace_chain(plan, direction, 0, ...) (next exec)
  *   "native_mixed"     1 (default): lengths that are not powers of two but have a mixed-radix configuration run the
  *                      native chain; 0: they run the Bluestein kernel like every other length (A/B runs, tests)
  *   "debug_skip"       measurement only, a bit set: bit 0 (value 1) = every pass skips its transform and becomes a copy with
@@ -330,10 +339,36 @@ typedef struct dfft_chain_step {
                              * 4 real z lines out (C2R), 5 real strided lines in (R2C) */
     int32_t exchange;       /* 0, or 1 / 2: that exchange after every chunk, dst -> the next step's src, with the tables
                              * dfft_get_pipeline_tables reports for the exec's direction */
+    int32_t split;          /* the same for every step of a chain: 1 if its chunks may alternate over two compute streams (option
+                             * "compute_streams") */
 } dfft_chain_step;
 /* the steps of the chain the next exec in `direction` of `dims` dimensions (1, 2: exec_dim's partial transforms; 3: the whole
  * transform) would run, as options read at exec time choose it; *count receives the number of steps, at most `capacity` are written */
 int dfft_debug_get_chain(const dfft_plan *plan, int direction, int dims, dfft_chain_step *steps, int capacity, int *count);
+/* One operation of the stream and event schedule of an exec (dfft_debug_trace_chain), in the order the exec issues them.  The executor
+ * (run_chain, csrc/dfft.hip) has one loop that decides the schedule; its launches, exchanges, event records and stream waits go through
+ * a sink that either issues them or only lists them, so this list is what an exec does, not a restatement of it.  Operations on one
+ * stream run in the order issued; a wait orders its stream behind the latest record of that event issued before it.  Fields that do not
+ * apply to a kind are -1 (which, scratch: 0). */
+typedef struct dfft_trace_op {
+    int32_t kind;           /* 0 launch, 1 exchange, 2 event record, 3 stream wait */
+    int32_t stream;         /* 0 the plan's stream (dfft_set_stream), 1 second compute stream, 2 communication stream, 3 second
+                             * communication stream */
+    int32_t event;          /* record / wait: number of the event within this exec */
+    int32_t step, chunk;    /* launch / exchange: index into dfft_debug_get_chain's steps, pipeline chunk */
+    int32_t launch;         /* launch: index within its group (what dfft_debug_get_pass takes) */
+    int32_t src, dst;       /* as in dfft_chain_step; exchange: send buffer, receive buffer */
+    int32_t which;          /* exchange: 1 / 2 */
+    int32_t scratch;        /* launch: 1 if it goes through the plan's shared level scratch (two-level and long-Bluestein lines) */
+} dfft_trace_op;
+/* dims = 1, 2, 3: the schedule the next exec in `direction` of `dims` dimensions would issue, as the options and the transport
+ * stand now (host only; no device needed).  Whether the second compute stream and the communication streams are used is a predicate of
+ * the plan -- option "compute_streams", the chain, the pipeline depth, the level scratch, option "graph", the transport's
+ * concurrent channels -- that the exec evaluates in the same way; a stream it asks for is created when an exec first needs it.
+ * dims = 0: what the last exec in `direction` (whole or partial) issued while option "trace" was 1; empty if there was none.  (A
+ * replayed hipGraph, option "graph", issues nothing: the list stays that of the exec that was captured.)
+ * *count receives the number of operations, at most `capacity` are written. */
+int dfft_debug_trace_chain(const dfft_plan *plan, int direction, int dims, dfft_trace_op *ops, int capacity, int *count);
 /* the per-point address table the kernels use for a segmented side of that launch (store = 0: load
  * side, 1: store side); entry i = {base[i], ln[i], aux[i]} as documented for SegEntry.  *count receives
  * the number of points; at most `capacity` entries are written. */

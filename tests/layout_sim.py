@@ -23,11 +23,11 @@ MODES = ["c2c", "c2c", "c2c", "r2c", "c2r", "r2c"]      # by line form of a chai
 
 
 def _seg(starts, lens, bases, n):
-    s = 0
+    """segment of point n (a number or an array of points): its start, length and base"""
+    s = np.zeros(np.shape(n), dtype=np.int64)
     for q in range(1, len(starts)):
-        if n >= starts[q]:
-            s = q
-    return starts[s], lens[s], bases[s]
+        s = np.where(np.asarray(n) >= starts[q], q, s)
+    return np.asarray(starts, dtype=np.int64)[s], np.asarray(lens, dtype=np.int64)[s], np.asarray(bases, dtype=np.int64)[s]
 
 
 class Pass:
@@ -41,12 +41,16 @@ class Pass:
         self.TL = plan.getTileLines()
         self.l = ([int(v) for v in d.lstart[:d.lnseg]], [int(v) for v in d.llen[:d.lnseg]], [int(v) for v in d.lbase[:d.lnseg]])
         self.s = ([int(v) for v in d.sstart[:d.snseg]], [int(v) for v in d.slen[:d.snseg]], [int(v) for v in d.sbase[:d.snseg]])
-        self.ltab = plan.debugPointTable(name, index, False) if d.load_kind == TILED and d.lnseg >= 1 else None
-        self.stab = plan.debugPointTable(name, index, True) if d.store_kind in (S_SAME, S_TRANSPOSE) and d.snseg >= 1 else None
+        table = lambda store: np.array(plan.debugPointTable(name, index, store), dtype=np.int64).reshape(-1, 3).T      # noqa: E731
+        self.ltab = table(False) if d.load_kind == TILED and d.lnseg >= 1 else None       # rows: base, ln, aux; one column per point
+        self.stab = table(True) if d.store_kind in (S_SAME, S_TRANSPOSE) and d.snseg >= 1 else None
 
     def tile(self, line):
-        b, l = divmod(line, self.TL)
-        return b, l, min(self.TL, self.d.LB - b * self.TL)
+        b, l = np.divmod(line, self.TL)
+        return b, l, np.minimum(self.TL, self.d.LB - b * self.TL)
+
+    # load_offset / store_offset: element offset of point n (k) of line (a, line); `line` and n may be arrays that broadcast
+    # (footprint: a column of lines against a row of points)
 
     def load_offset(self, a, line, n, NP):
         d, TL = self.d, self.TL
@@ -60,8 +64,8 @@ class Pass:
             assert d.lnseg == 1
             return bs + a * d.IA + b * d.IB + (n - s0) * tw + l
         off = bs + a * ln * d.LB + b * TL * ln + (n - s0) * tw + l
-        base, tln, aux = self.ltab[n]            # the per-point table must say the same
-        assert off == base + tln * (a * d.LB + b * TL) + aux * tw + l
+        base, tln, aux = self.ltab[:, n]            # the per-point table must say the same
+        assert np.all(off == base + tln * (a * d.LB + b * TL) + aux * tw + l)
         return off
 
     def store_offset(self, a, line, k, NP):
@@ -72,38 +76,59 @@ class Pass:
         if d.store_kind == S_KMAJOR:
             return k * d.KS_out + a * d.AS_out + line
         s0, ln, bs = _seg(*self.s, k)
-        base, tln, aux = self.stab[k]
+        base, tln, aux = self.stab[:, k]
         if d.store_kind == S_SAME:
             sk, sb = (d.SK or d.LB * d.LA), (d.SB or TL * d.LA)
             off = bs + (k - s0) * sk + b * sb + a * tw + l
-            assert off == base + b * sb + a * tw + l
+            assert np.all(off == base + b * sb + a * tw + l)
             return off
         T2 = 1 << d.T2shift
         kt, kr = (k - s0) >> d.T2shift, (k - s0) & (T2 - 1)
-        tw2 = min(T2, ln - kt * T2)
+        tw2 = np.minimum(T2, ln - kt * T2)
         off = bs + a * ln * d.LB + kt * T2 * d.LB + line * tw2 + kr
-        assert off == base + tln * (a * d.LB) + line * aux
+        assert np.all(off == base + tln * (a * d.LB) + line * aux)
         return off
+
+    def sides(self, N, mode):
+        """points per line and elements skipped by in_off / out_off (in elements of that side's type) on the load and the store side"""
+        d = self.d
+        nin = N // 2 + 1 if mode == "c2r" else N
+        nout = N // 2 + 1 if mode == "r2c" else N
+        return nin, nout, d.in_off // (self.esz // 2 if mode == "r2c" else self.esz), d.out_off // (self.esz // 2 if mode == "c2r" else self.esz)
 
     def run(self, src, dst, N, mode="c2c"):
         """mode: c2c (N complex points), r2c (N reals in -> N//2+1 out), c2r (N//2+1 in -> N reals out).
         src / dst are flat numpy arrays of the element type of that side."""
         d = self.d
-        nin = N // 2 + 1 if mode == "c2r" else N
-        nout = N // 2 + 1 if mode == "r2c" else N
-        src = src[d.in_off // (self.esz // 2 if mode == "r2c" else self.esz):]
-        dst = dst[d.out_off // (self.esz // 2 if mode == "c2r" else self.esz):]
+        nin, nout, ioff, ooff = self.sides(N, mode)
+        src = src[ioff:]
+        dst = dst[ooff:]
         for a in range(d.na):
             for line in range(d.LB):
-                x = np.array([src[self.load_offset(a, line, n, nin)] for n in range(nin)])
+                x = src[self.load_offset(a, line, np.arange(nin), nin)]
                 if mode == "r2c":
                     y = np.fft.rfft(x.real, N)
                 elif mode == "c2r":
                     y = np.fft.irfft(x, N) * N
                 else:
                     y = np.fft.ifft(x) * N if d.swap else np.fft.fft(x)
-                for k in range(nout):
-                    dst[self.store_offset(a, line, k, nout)] = y[k]
+                dst[self.store_offset(a, line, np.arange(nout), nout)] = y[:nout]
+
+    def footprint(self, N, mode="c2c"):
+        """(loads, stores): what the launch reads from its source and writes to its destination buffer, as sorted arrays of indices in
+        units of one REAL element from the start of the buffer (a complex element is two of them; real sides are half as wide).  The
+        addresses are those of run(): load_offset / store_offset over every (a, line, point), per-point-table assertions included."""
+        d = self.d
+        nin, nout, ioff, ooff = self.sides(N, mode)
+        wi, wo = (1 if mode == "r2c" else 2), (1 if mode == "c2r" else 2)
+        cat = lambda v: np.concatenate(v + [np.zeros(0, dtype=np.int64)]).astype(np.int64)      # noqa: E731
+        lines = np.arange(d.LB, dtype=np.int64)[:, None]
+        ld = cat([np.ravel(self.load_offset(a, lines, np.arange(nin)[None, :], nin)) for a in range(d.na)])
+        st = cat([np.ravel(self.store_offset(a, lines, np.arange(nout)[None, :], nout)) for a in range(d.na)])
+        ld, st = (ld + ioff) * wi, (st + ooff) * wo
+        assert len(np.unique(st)) == len(st), "a launch stores twice to one element"
+        widen = lambda v, w: np.unique(v if w == 1 else np.concatenate([v, v + 1]))      # noqa: E731
+        return widen(ld, wi), widen(st, wo)
 
 
 class World:

@@ -668,16 +668,33 @@ def test_address_table_modes_agree(mode, monkeypatch):
 # ------------------------------------------------------------------------------------------
 # option compute_streams = 2: the pipeline chunks of a pass alternate over two compute streams
 # ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("chunks", [2, 3, 4, 8])
-@pytest.mark.parametrize("shape,P1,P2", [((32, 32, 32), 2, 4), ((16, 16, 16), 3, 2), ((64, 32, 16), 8, 1), ((16, 32, 16), 1, 4), ((128, 64, 32), 2, 4)])
+def used_stream_1(plans):
+    """from what the last forward and inverse exec of every rank issued (option trace): did any of them use the second compute stream"""
+    issued = [pl.debugTrace(d, 0) for pl in plans for d in (dfft.FORWARD, dfft.INVERSE)]
+    assert all(issued)
+    return any(o["stream"] == 1 for t in issued for o in t)
+
+
+# small grids at every depth, and one pencil and one slab grid large enough that a chunk's kernels are not launch-bound (256 x 256 x 128
+# fp64: 0.27 GB per buffer over all virtual ranks), so that the two streams really overlap
+TWO_STREAM_SMALL = [((32, 32, 32), 2, 4), ((16, 16, 16), 3, 2), ((64, 32, 16), 8, 1), ((16, 32, 16), 1, 4), ((128, 64, 32), 2, 4)]
+TWO_STREAM_LARGE = [((256, 256, 128), 2, 4, 4), ((256, 256, 128), 8, 1, 4)]
+TWO_STREAM_CASES = [pytest.param(s, P1, P2, c, id=f"shape{i}-{P1}-{P2}-{c}") for c in (2, 3, 4, 8) for i, (s, P1, P2) in enumerate(TWO_STREAM_SMALL)] + \
+                   [pytest.param(s, P1, P2, c, id=f"shape{len(TWO_STREAM_SMALL) + i}-{P1}-{P2}-{c}") for i, (s, P1, P2, c) in enumerate(TWO_STREAM_LARGE)]
+
+
+@pytest.mark.parametrize("shape,P1,P2,chunks", TWO_STREAM_CASES)
 def test_two_compute_streams_are_bit_identical_to_one(shape, P1, P2, chunks):
     """the same kernels on the same data in another stream assignment: spectrum and round trip must not change by one bit
-    (a missing dependency between the two compute streams shows up as a difference or as a wrong result against the oracle)"""
-    ref = run_distributed(shape, P1, P2, "double", chunks=chunks, options={"compute_streams": 1})
+    (a missing dependency between the two compute streams shows up as a difference or as a wrong result against the oracle);
+    the trace of what was issued says that the two-stream runs used the second stream and the one-stream run did not"""
+    ref = run_distributed(shape, P1, P2, "double", chunks=chunks, options={"compute_streams": 1, "trace": 1})
+    assert not used_stream_1(ref[0])
     want = orc.fft3d_c2c(orc.fill_block(shape, (0, 0, 0), shape, 2, seed=7), -1)
     for _ in range(3):          # scheduling varies from run to run
-        two = run_distributed(shape, P1, P2, "double", chunks=chunks, options={"compute_streams": 2})
+        two = run_distributed(shape, P1, P2, "double", chunks=chunks, options={"compute_streams": 2, "trace": 1})
         assert two[0][0].getOption("compute_streams") == 2
+        assert used_stream_1(two[0])
         for r in range(P1 * P2):
             assert np.array_equal(two[2][r], ref[2][r]) and np.array_equal(two[3][r], ref[3][r])
     for r, pl in enumerate(ref[0]):
@@ -685,10 +702,12 @@ def test_two_compute_streams_are_bit_identical_to_one(shape, P1, P2, chunks):
         check_forward(ref[2][r], want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]], "double", want.size, want_rms=rms(want), zero_mean=False)
 
 
-@pytest.mark.parametrize("shape,P1,P2", [((32, 32, 32), 2, 4), ((64, 32, 16), 4, 1), ((16, 32, 64), 1, 4)])
+@pytest.mark.parametrize("shape,P1,P2", [((32, 32, 32), 2, 4), ((64, 32, 16), 4, 1), ((16, 32, 64), 1, 4), ((256, 256, 128), 2, 4), ((256, 256, 128), 8, 1)])
 def test_two_compute_streams_r2c_bit_identical(shape, P1, P2):
-    ref = run_distributed_real(shape, P1, P2, "double", options={"compute_streams": 1})
+    ref = run_distributed_real(shape, P1, P2, "double", options={"compute_streams": 1, "trace": 1})
+    assert not used_stream_1(ref[0])
     for _ in range(3):
-        two = run_distributed_real(shape, P1, P2, "double", options={"compute_streams": 2})
+        two = run_distributed_real(shape, P1, P2, "double", options={"compute_streams": 2, "trace": 1})
+        assert used_stream_1(two[0])
         for r in range(P1 * P2):
             assert np.array_equal(two[2][r], ref[2][r]) and np.array_equal(two[3][r], ref[3][r])
