@@ -49,19 +49,21 @@ static bool pass_info(int prec, int N, PassInfo *pi)
     return prec == DFFT_F64 ? pass_info_f64(N, 0, pi) : pass_info_f32(N, 0, pi);
 }
 
+#ifdef DFFT_EXPERIMENTS
+// A/B build only (make exp): DFFT_EXP_F32_TWIDDLES=1 rounds every fp64 table -- tw, twN, tw_zr (make_twiddles), the Bluestein chirp
+// and bhat (upload_complex) -- through fp32: the defect the per-entry forward bound of tests/parity_metric.py has to catch
+// (profiles/r6_f32_twiddle_proof.txt, profiles/entry_parity_mutation.txt); the shipped library has no such switch
+static const bool f32_tw = [] { const char *e = getenv("DFFT_EXP_F32_TWIDDLES"); return e && atoi(e) != 0; }();
+#else
+constexpr bool f32_tw = false;
+#endif
+
 // twiddle table exp(-2*pi*i*j/N), evaluated in long double, rounded once
 static int make_twiddles(int prec, size_t N, void **dev)
 {
     const long double PI = 3.141592653589793238462643383279502884L;
     const size_t esz = prec == DFFT_F64 ? 16 : 8;
     std::vector<char> host(esz * N);
-#ifdef DFFT_EXPERIMENTS
-    // A/B build only (make exp): DFFT_EXP_F32_TWIDDLES=1 rounds the fp64 table through fp32 -- the defect the per-entry forward
-    // bound of tests/parity_metric.py has to catch (profiles/r6_f32_twiddle_proof.txt); the shipped library has no such switch
-    static const bool f32_tw = [] { const char *e = getenv("DFFT_EXP_F32_TWIDDLES"); return e && atoi(e) != 0; }();
-#else
-    constexpr bool f32_tw = false;
-#endif
     for (size_t j = 0; j < N; j++) {
         long double a = -2.0L * PI * (long double)j / (long double)N;
         if (prec == DFFT_F64) {
@@ -110,6 +112,7 @@ static int upload_complex(int prec, const std::vector<std::complex<long double>>
         if (prec == DFFT_F64) {
             double *d = reinterpret_cast<double *>(buf.data()) + 2 * j;
             d[0] = (double)h[j].real(); d[1] = (double)h[j].imag();
+            if (f32_tw) { d[0] = (double)(float)d[0]; d[1] = (double)(float)d[1]; }
         } else {
             float *d = reinterpret_cast<float *>(buf.data()) + 2 * j;
             d[0] = (float)h[j].real(); d[1] = (float)h[j].imag();

@@ -14,7 +14,7 @@ torch = pytest.importorskip("torch")
 import distributedfft_amd as dfft  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 
-from parity_metric import CENTER, check_forward, rms  # noqa: E402
+from parity_metric import CENTER, check_forward, check_forward_blocks, rms  # noqa: E402
 
 TOL_FWD = {"double": 1e-11, "float": 1e-4}
 TOL_RT = {"double": 1e-10, "float": 5e-5}
@@ -306,37 +306,40 @@ def test_pipelined_exchange_chunks(shape, P1, P2, chunks):
         ref = want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]]
         assert np.max(np.abs(spec[r] - ref)) / np.max(np.abs(want)) < 1e-11
         assert rel(backs[r] / n3, ins[r]) < 1e-10
+    check_forward_blocks(plans, spec, want, "double", want.size, zero_mean=False)
 
 
 # ------------------------------------------------------------------------------------------
 # partial transforms: MPIcuFFT_Pencil::execR2C/execC2R(out, in, d), d = 1, 2
 # (reference tests random_dist_1D.cu:180-451, random_dist_2D.cu:181-455)
 # ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("c2c", [False, True])
-@pytest.mark.parametrize("shape,P1,P2", [((16, 16, 16), 1, 1), ((32, 32, 32), 2, 4), ((16, 32, 64), 3, 2), ((64, 32, 16), 4, 1)])
-@pytest.mark.parametrize("d", [1, 2])
-@pytest.mark.parametrize("two_level", [0, 1])
-def test_partial_dimension_transforms(shape, P1, P2, d, c2c, two_level):
-    """execR2C / execC2R(out, in, d) (src/pencil/mpicufft_pencil.cpp:1644-1839); two_level = 1: the same on two-level lines"""
+def run_partial(shape, P1, P2, d, c2c, two_level=0, prec="double", center=False, seed=31):
+    """execC2C / execR2C(out, in, d) and back on P1*P2 virtual ranks: (plans, global input, per-rank (got, want) blocks of the partial
+    spectrum, the whole partial spectrum, inputs, round trips); the reference is numpy's transform along z (d = 1), then y (d = 2)"""
     P = P1 * P2
     world = dfft.Comm.local(P) if P > 1 else None
     Nx, Ny, Nz = shape
     Nzc = Nz if c2c else Nz // 2 + 1
-    g = orc.fill_block(shape, (0, 0, 0), shape, 2 if c2c else 1, seed=31)
+    esz = 16 if prec == "double" else 8
+    g = orc.fill_block(shape, (0, 0, 0), shape, 2 if c2c else 1, seed=seed)
+    if center:
+        g = g - (CENTER * (1 + 1j) if c2c else CENTER)
+    g = g.astype(NPDT[prec] if c2c else NPR[prec])
+    g64 = g.astype(np.complex128 if c2c else np.float64)
     # d = 1: FFT along z only; d = 2: along z then y (numpy as the independent reference)
-    ref = np.fft.fft(g, axis=2) if c2c else np.fft.rfft(g, axis=2)
+    ref = np.fft.fft(g64, axis=2) if c2c else np.fft.rfft(g64, axis=2)
     if d == 2:
         ref = np.fft.fft(ref, axis=1)
     plans, ins, outs, backs = [], [], [], []
     for r in range(P):
-        pl = dfft.MPIcuFFT_Pencil(dfft.Configurations(), world, precision="double", rank=r)
+        pl = dfft.MPIcuFFT_Pencil(dfft.Configurations(), world, precision=prec, rank=r)
         pl.setOption("two_level", two_level)
         pl.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(P1, P2), True, c2c=c2c)
         s, o = pl.getInSize(), pl.getInStart()
         blk = np.ascontiguousarray(g[o[0]:o[0] + s[0], o[1]:o[1] + s[1], :])
         plans.append(pl)
         ins.append(torch.from_numpy(blk).cuda())
-        outs.append(torch.zeros(pl.getDomainSize() // 16, dtype=torch.complex128, device="cuda"))
+        outs.append(torch.zeros(pl.getDomainSize() // esz, dtype=CDT[prec], device="cuda"))
         backs.append(torch.zeros_like(ins[-1]))
     torch.cuda.synchronize()
 
@@ -355,7 +358,7 @@ def test_partial_dimension_transforms(shape, P1, P2, d, c2c, two_level):
     with ThreadPoolExecutor(P) as ex:
         list(ex.map(fwd, range(P)))
     torch.cuda.synchronize()
-    scale = np.max(np.abs(ref))
+    blocks = []
     for r, pl in enumerate(plans):
         isz, ist = pl.getInSize(), pl.getInStart()
         osz, ost = pl.getOutSize(), pl.getOutStart()
@@ -365,14 +368,30 @@ def test_partial_dimension_transforms(shape, P1, P2, d, c2c, two_level):
         else:           # [xs][Ny][zs]
             shp = (isz[0], Ny, osz[2])
             want = ref[ist[0]:ist[0] + isz[0], :, ost[2]:ost[2] + osz[2]]
-        got = outs[r][:int(np.prod(shp))].cpu().numpy().reshape(shp)
-        assert np.max(np.abs(got - want)) / scale < 1e-11
+        blocks.append((outs[r][:int(np.prod(shp))].cpu().numpy().reshape(shp), want))
     with ThreadPoolExecutor(P) as ex:
         list(ex.map(inv, range(P)))
     torch.cuda.synchronize()
-    norm = float(Nz if d == 1 else Nz * Ny)
-    for r in range(P):
-        assert rel(backs[r].cpu().numpy() / norm, ins[r].cpu().numpy()) < 1e-10
+    return plans, blocks, ref, [t.cpu().numpy() for t in ins], [t.cpu().numpy() for t in backs]
+
+
+@pytest.mark.parametrize("c2c", [False, True])
+@pytest.mark.parametrize("shape,P1,P2", [((16, 16, 16), 1, 1), ((32, 32, 32), 2, 4), ((16, 32, 64), 3, 2), ((64, 32, 16), 4, 1)])
+@pytest.mark.parametrize("d", [1, 2])
+@pytest.mark.parametrize("two_level", [0, 1])
+def test_partial_dimension_transforms(shape, P1, P2, d, c2c, two_level):
+    """execR2C / execC2R(out, in, d) (src/pencil/mpicufft_pencil.cpp:1644-1839); two_level = 1: the same on two-level lines"""
+    Nx, Ny, Nz = shape
+    plans, blocks, ref, ins, backs = run_partial(shape, P1, P2, d, c2c, two_level)
+    scale = np.max(np.abs(ref))
+    points = Nz if d == 1 else Nz * Ny        # the transform applied: lines along z, or (y, z) planes
+    ref_rms = rms(ref)
+    for got, want in blocks:
+        assert np.max(np.abs(got - want)) / scale < 1e-11
+        check_forward(got, want, "double", points, want_rms=ref_rms, zero_mean=False)
+    norm = float(points)
+    for r in range(P1 * P2):
+        assert rel(backs[r] / norm, ins[r]) < 1e-10
 
 
 # ------------------------------------------------------------------------------------------
@@ -385,15 +404,19 @@ def test_fft1d_any_length_vs_oracle(N, prec):
     """variant -1 = the Bluestein kernel for every length (also those that have a native mixed-radix configuration)"""
     batch = 45
     rng = np.random.default_rng(N)
-    x = (rng.uniform(0, 255, (batch, N)) + 1j * rng.uniform(0, 255, (batch, N))).astype(NPDT[prec])
-    d_in = torch.from_numpy(x).cuda()
-    d_out = torch.zeros_like(d_in)
-    for direction in (dfft.FORWARD, dfft.INVERSE):
-        torch.cuda.synchronize()
-        dfft.fft1d_batched(d_out, d_in, N, batch, direction, prec, variant=-1)
-        torch.cuda.synchronize()
-        want = orc.fft1d(x.astype(np.complex128), direction)
-        assert rel(d_out.cpu().numpy(), want) < (2e-11 if prec == "double" else 2e-4)
+    x0 = rng.uniform(0, 255, (batch, N)) + 1j * rng.uniform(0, 255, (batch, N))
+    for centred, x in ((False, x0.astype(NPDT[prec])), (True, (x0 - CENTER * (1 + 1j)).astype(NPDT[prec]))):      # the reference's distribution, and the same centred
+        d_in = torch.from_numpy(x).cuda()
+        d_out = torch.zeros_like(d_in)
+        for direction in (dfft.FORWARD, dfft.INVERSE):
+            torch.cuda.synchronize()
+            dfft.fft1d_batched(d_out, d_in, N, batch, direction, prec, variant=-1)
+            torch.cuda.synchronize()
+            want = orc.fft1d(x.astype(np.complex128), direction)
+            # per entry (parity_metric.py): the inverse of a line is a transform like any other
+            check_forward(d_out.cpu().numpy(), want, prec, N, zero_mean=centred,
+                          label=f"Bluestein fft1d N={N} dir={direction} centred={centred}" if N == 4095 else None)
+            assert rel(d_out.cpu().numpy(), want) < (2e-11 if prec == "double" else 2e-4)
 
 
 def mixed_lengths(prec):
@@ -416,15 +439,18 @@ def test_fft1d_mixed_radix_lengths_vs_oracle(prec):
         assert info is not None and info["threads"] * info["points_per_thread"] == N * info["lines_per_workgroup"], (N, info)
         batch = 19 if N >= 256 else 77
         rng = np.random.default_rng(N)
-        x = (rng.uniform(0, 255, (batch, N)) + 1j * rng.uniform(0, 255, (batch, N))).astype(NPDT[prec])
-        d_in = torch.from_numpy(x).cuda()
-        d_out = torch.zeros_like(d_in)
-        for direction in (dfft.FORWARD, dfft.INVERSE):
-            torch.cuda.synchronize()
-            dfft.fft1d_batched(d_out, d_in, N, batch, direction, prec)
-            torch.cuda.synchronize()
-            want = orc.fft1d(x.astype(np.complex128), direction)
-            assert rel(d_out.cpu().numpy(), want) < (2e-11 if prec == "double" else 2e-4), (N, direction)
+        x0 = rng.uniform(0, 255, (batch, N)) + 1j * rng.uniform(0, 255, (batch, N))
+        for centred, x in ((False, x0.astype(NPDT[prec])), (True, (x0 - CENTER * (1 + 1j)).astype(NPDT[prec]))):      # the reference's distribution, and the same centred
+            d_in = torch.from_numpy(x).cuda()
+            d_out = torch.zeros_like(d_in)
+            for direction in (dfft.FORWARD, dfft.INVERSE):
+                torch.cuda.synchronize()
+                dfft.fft1d_batched(d_out, d_in, N, batch, direction, prec)
+                torch.cuda.synchronize()
+                want = orc.fft1d(x.astype(np.complex128), direction)
+                check_forward(d_out.cpu().numpy(), want, prec, N, zero_mean=centred,
+                              label=f"mixed radix fft1d N={N} dir={direction} centred={centred}" if N == lengths[-1] else None)
+                assert rel(d_out.cpu().numpy(), want) < (2e-11 if prec == "double" else 2e-4), (N, direction)
 
 
 @pytest.mark.parametrize("prec", ["double", "float"])
@@ -445,6 +471,7 @@ def test_mixed_radix_r2c_c2r_vs_oracle_and_bluestein(shape, P1, P2, prec):
         ref = want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]]
         assert np.max(np.abs(spec[r] - ref)) / scale < tol_f
         assert rel(backs[r] / n3, ins[r]) < tol_r
+    check_forward_blocks(plans, spec, want, prec, g.size, zero_mean=False)
     if max(shape) <= 1024:
         _, _, spec_b, _ = run_distributed_real(shape, P1, P2, prec, options={"native_mixed": 0})
         for r in range(len(plans)):
@@ -468,6 +495,7 @@ def test_mixed_radix_grids_vs_oracle_and_bluestein(shape, P1, P2, prec):
         ref = want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]]
         assert np.max(np.abs(spec[r] - ref)) / np.max(np.abs(want)) < tol_f
         assert rel(backs[r] / n3, ins[r]) < tol_r
+    check_forward_blocks(plans, spec, want, prec, want.size, zero_mean=False)
     if max(shape) <= 1024:
         plans_b, _, spec_b, _ = run_distributed(shape, P1, P2, prec, options={"native_mixed": 0})
         for r in range(len(plans)):
@@ -480,6 +508,7 @@ def test_single_rank_any_size_vs_oracle_and_golden(shape):
     g, got, back = run_single(shape, "double", seed=20260921)
     want = orc.fft3d_c2c(g, -1)
     assert rel(got, want) < 2e-11
+    check_forward(got, want, "double", g.size, zero_mean=False)
     assert rel(back / g.size, g) < 1e-10
     if shape == (12, 10, 14):
         d = np.load(os.path.join(GOLD, "fft3d_small.npz"))
@@ -499,6 +528,7 @@ def test_distributed_any_size_c2c_and_r2c(shape, P1, P2):
         ref = want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]]
         assert np.max(np.abs(spec[r] - ref)) / np.max(np.abs(want)) < 2e-11
         assert rel(backs[r] / n3, ins[r]) < 1e-10
+    check_forward_blocks(plans, spec, want, "double", want.size, zero_mean=False)
     for shp in (shape, (shape[0], shape[1], shape[2] + 1)):
         plans, ins, spec, backs = run_distributed_real(shp, P1, P2, "double")
         wantr = orc.fft3d_r2c(orc.fill_block(shp, (0, 0, 0), shp, 1, seed=13))
@@ -508,6 +538,7 @@ def test_distributed_any_size_c2c_and_r2c(shape, P1, P2):
             ref = wantr[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]]
             assert np.max(np.abs(spec[r] - ref)) / np.max(np.abs(wantr)) < 2e-11
             assert rel(backs[r] / n3, ins[r]) < 1e-10
+        check_forward_blocks(plans, spec, wantr, "double", int(n3), zero_mean=False)
 
 
 @pytest.mark.parametrize("c2c", [True, False])
@@ -628,6 +659,7 @@ def test_randomised_sweep_of_shapes_partitions_and_depths():
             ref = want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]]
             assert np.max(np.abs(spec[r] - ref)) / scale < 2e-11, (shape, P1, P2, chunks, c2c, r)
             assert rel(backs[r] / n3, ins[r]) < 1e-10, (shape, P1, P2, chunks, c2c, r)
+        check_forward_blocks(plans, spec, want, "double", int(n3), zero_mean=False)
         done += 1
 
 
@@ -642,6 +674,7 @@ def test_sixteen_and_eighteen_ranks(shape, P1, P2):
         ref = want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]]
         assert np.max(np.abs(spec[r] - ref)) / np.max(np.abs(want)) < 2e-11
         assert rel(backs[r] / n3, ins[r]) < 1e-10
+    check_forward_blocks(plans, spec, want, "double", want.size, zero_mean=False)
 
 
 @pytest.mark.parametrize("mode", ["0", "2"])
@@ -658,11 +691,13 @@ def test_address_table_modes_agree(mode, monkeypatch):
             s, o = pl.getOutSize(), pl.getOutStart()
             assert np.max(np.abs(spec[r] - want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]])) / np.max(np.abs(want)) < 1e-11
             assert rel(backs[r] / n3, ins[r]) < 1e-10
+        check_forward_blocks(plans, spec, want, "double", want.size, zero_mean=False)
     plans, ins, spec, backs = run_distributed_real((32, 16, 64), 2, 2, "float")
     wantr = orc.fft3d_r2c(orc.fill_block((32, 16, 64), (0, 0, 0), (32, 16, 64), 1, seed=13).astype(np.float32).astype(np.float64))
     for r, pl in enumerate(plans):
         s, o = pl.getOutSize(), pl.getOutStart()
         assert np.max(np.abs(spec[r] - wantr[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]])) / np.max(np.abs(wantr)) < 1e-4
+    check_forward_blocks(plans, spec, wantr, "float", 32 * 16 * 64, zero_mean=False)      # fp32, non-negative input: recorded only
 
 
 # ------------------------------------------------------------------------------------------

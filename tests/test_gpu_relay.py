@@ -14,7 +14,8 @@ torch = pytest.importorskip("torch")
 import distributedfft_amd as dfft  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 
-from test_gpu_parity import NPDT, TOL_FWD, TOL_RT, rel, run_distributed, run_distributed_real  # noqa: E402
+from parity_metric import check_forward_blocks  # noqa: E402
+from test_gpu_parity import NPDT, NPR, TOL_FWD, TOL_RT, rel, run_distributed, run_distributed_real  # noqa: E402
 
 CASES = [((128, 64, 32), 2, 4), ((66, 50, 38), 2, 4), ((64, 64, 64), 3, 2), ((48, 40, 56), 4, 2), ((40, 36, 30), 2, 3)]
 
@@ -35,6 +36,7 @@ def test_relayed_exchange_is_bit_identical_to_the_direct_one(shape, P1, P2, chun
         assert np.array_equal(backs_d[r], backs_r[r]), (r, "round trip differs from the direct exchange")
         assert np.max(np.abs(spec_r[r] - want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]])) / scale < TOL_FWD[prec]
         assert rel(backs_r[r] / float(np.prod(shape)), ins[r]) < TOL_RT[prec]
+    check_forward_blocks(plans, spec_r, want, prec, g.size, zero_mean=False)
 
 
 @pytest.mark.parametrize("prec", ["double", "float"])
@@ -43,9 +45,14 @@ def test_relayed_r2c_c2r(shape, P1, P2, prec):
     """the reference's own API (execR2C / execC2R) with the uneven Nz/2 + 1 split: 33 = 9 + 8 + 8 + 8"""
     plans, ins, spec_d, backs_d = run_distributed_real(shape, P1, P2, prec)
     _, _, spec_r, backs_r = run_distributed_real(shape, P1, P2, prec, comm_options={"relay": 3})
-    for r in range(len(plans)):
+    g = orc.fill_block(shape, (0, 0, 0), shape, 1, seed=13).astype(NPR[prec]).astype(np.float64)
+    want = orc.fft3d_r2c(g)
+    for r, pl in enumerate(plans):
+        s, o = pl.getOutSize(), pl.getOutStart()
         assert np.array_equal(spec_d[r], spec_r[r]) and np.array_equal(backs_d[r], backs_r[r])
+        assert np.max(np.abs(spec_r[r] - want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]])) / np.max(np.abs(want)) < TOL_FWD[prec]
         assert rel(backs_r[r] / float(np.prod(shape)), ins[r]) < TOL_RT[prec]
+    check_forward_blocks(plans, spec_r, want, prec, g.size, zero_mean=False)
 
 
 def test_relay_option_values():

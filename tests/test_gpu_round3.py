@@ -25,7 +25,7 @@ torch = pytest.importorskip("torch")
 import distributedfft_amd as dfft  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 
-from parity_metric import CENTER, entry_rel, forward_bound, record  # noqa: E402
+from parity_metric import CENTER, check_forward, check_forward_blocks, entry_rel, forward_bound, record  # noqa: E402
 from test_gpu_fullsize import direct_dft_entry, host_rms, make_world, owner_entry, run_all, spectrum_block  # noqa: E402
 from test_gpu_parity import (CDT, NPDT, NPR, TOL_FWD, TOL_RT, rel, run_distributed, run_distributed_real,  # noqa: E402
                              run_single)
@@ -417,8 +417,11 @@ def test_c5_shaped_2048x2048x1024_fp32_pencil_2x4_every_point():
 # ------------------------------------------------------------------------------------------
 # single-rank pass order z, x, y, forced
 # ------------------------------------------------------------------------------------------
-def run_single_order(shape, prec, options, seed=5):
-    g = orc.fill_block(shape, (0, 0, 0), shape, 2, seed=seed).astype(NPDT[prec])
+def run_single_order(shape, prec, options, seed=5, center=False):
+    g = orc.fill_block(shape, (0, 0, 0), shape, 2, seed=seed)
+    if center:
+        g = g - CENTER * (1 + 1j)
+    g = g.astype(NPDT[prec])
     plan = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), precision=prec)
     for k, v in options.items():
         plan.setOption(k, v)
@@ -453,6 +456,7 @@ def test_single_order_zxy_forced_vs_oracle(shape, layout, pad, prec):
     g, got, back = run_single_order(shape, prec, {"single_order": 1, "single_layout": layout, "single_pad": pad})
     want = orc.fft3d_c2c(g.astype(np.complex128), -1)
     assert rel(got, want) < 2 * TOL_FWD[prec]
+    check_forward(got, want, prec, g.size, zero_mean=False)
     assert rel(back / g.size, g) < TOL_RT[prec]
 
 
@@ -493,6 +497,7 @@ def test_every_mixed_real_z_pass_vs_oracle(prec):
             s, o = pl.getOutSize(), pl.getOutStart()
             assert np.max(np.abs(spec[r] - want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]])) / scale < tol_f, M
             assert rel(backs[r] / float(np.prod(shape)), ins[r]) < tol_r, M
+        check_forward_blocks(plans, spec, want, prec, g.size, zero_mean=False)
 
 
 # ------------------------------------------------------------------------------------------
@@ -517,6 +522,7 @@ def test_uniform_table_reads_match_per_lane_reads(shape, P1, P2, chunks, prec):
         assert np.array_equal(backs_u[r], backs_v[r])
         assert np.max(np.abs(spec_u[r] - want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]])) / scale < TOL_FWD[prec]
         assert rel(backs_u[r] / float(np.prod(shape)), ins[r]) < TOL_RT[prec]
+    check_forward_blocks(plans, spec_u, want, prec, g.size, zero_mean=False)
 
 
 # ------------------------------------------------------------------------------------------
@@ -539,6 +545,7 @@ def test_scalar_base_addresses_match_vector_addresses_single_rank(shape, options
     assert np.array_equal(back_s, back_v)
     want = orc.fft3d_c2c(g.astype(np.complex128), -1)
     assert rel(got_s, want) < 2 * TOL_FWD[prec]
+    check_forward(got_s, want, prec, g.size, zero_mean=False)
     assert rel(back_s / g.size, g) < TOL_RT[prec]
 
 
@@ -558,6 +565,7 @@ def test_scalar_base_addresses_match_vector_addresses_distributed(shape, P1, P2,
         assert np.array_equal(backs_s[r], backs_v[r])
         assert np.max(np.abs(spec_s[r] - want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]])) / scale < TOL_FWD[prec]
         assert rel(backs_s[r] / float(np.prod(shape)), ins[r]) < TOL_RT[prec]
+    check_forward_blocks(plans, spec_s, want, prec, g.size, zero_mean=False)
 
 
 def test_variant_options_outside_the_key_range_are_rejected():

@@ -15,6 +15,8 @@ torch = pytest.importorskip("torch")
 import distributedfft_amd as dfft  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 
+from parity_metric import CENTER, check_forward_blocks  # noqa: E402
+
 TOL_FWD = {"double": 1e-11, "float": 1e-4}
 TOL_RT = {"double": 1e-10, "float": 5e-5}
 CDT = {"double": torch.complex128, "float": torch.complex64}
@@ -22,7 +24,7 @@ NPC = {"double": np.complex128, "float": np.complex64}
 NPR = {"double": np.float64, "float": np.float32}
 
 
-def run(cls, shape, P, prec, c2c, chunks=None, field=None, modify=None, seed=21, options=None):
+def run(cls, shape, P, prec, c2c, chunks=None, field=None, modify=None, seed=21, options=None, center=False):
     world = dfft.Comm.local(P) if P > 1 else None
     esz = 16 if prec == "double" else 8
     plans, ins, outs, backs, host_ins = [], [], [], [], []
@@ -38,9 +40,9 @@ def run(cls, shape, P, prec, c2c, chunks=None, field=None, modify=None, seed=21,
         if field is not None:
             blk = np.ascontiguousarray(field[start[0]:start[0] + size[0]]).astype(NPR[prec])
         elif c2c:
-            blk = orc.fill_block(shape, start, size, 2, seed=seed).astype(NPC[prec])
+            blk = (orc.fill_block(shape, start, size, 2, seed=seed) - (CENTER * (1 + 1j) if center else 0.0)).astype(NPC[prec])
         else:
-            blk = orc.fill_block(shape, start, size, 1, seed=seed).astype(NPR[prec])
+            blk = (orc.fill_block(shape, start, size, 1, seed=seed) - (CENTER if center else 0.0)).astype(NPR[prec])
         plans.append(pl)
         host_ins.append(blk.copy())
         ins.append(torch.from_numpy(blk).cuda())
@@ -71,8 +73,10 @@ def run(cls, shape, P, prec, c2c, chunks=None, field=None, modify=None, seed=21,
     return plans, [t.cpu().numpy() for t in ins], spec, [t.cpu().numpy() for t in backs]
 
 
-def global_input(shape, c2c, prec, seed=21):
+def global_input(shape, c2c, prec, seed=21, center=False):
     g = orc.fill_block(shape, (0, 0, 0), shape, 2 if c2c else 1, seed=seed)
+    if center:      # what run / run_yzx subtract with center=True
+        g = g - (CENTER * (1 + 1j) if c2c else CENTER)
     return g.astype(NPC[prec]).astype(np.complex128) if c2c else g.astype(NPR[prec]).astype(np.float64)
 
 
@@ -100,6 +104,7 @@ def test_z_then_yx_vs_oracle(shape, P, c2c, prec):
         assert np.max(np.abs(spec[r] - ref)) / scale < TOL_FWD[prec]
         assert np.max(np.abs(backs[r] / n3 - ins[r])) / 255.0 < TOL_RT[prec]
     assert np.all(cover == 1)
+    check_forward_blocks(plans, spec, want, prec, int(n3), zero_mean=False)
 
 
 @pytest.mark.parametrize("chunks", [1, 2, 3, 8])
@@ -161,7 +166,7 @@ def test_z_then_yx_errors_and_single_rank():
 # ------------------------------------------------------------------------------------------
 # Y_Then_ZX (src/slab/y_then_zx/): R2C along y, output [Nx][(Ny/2+1)/P][Nz], forward only
 # ------------------------------------------------------------------------------------------
-def run_yzx(shape, P, prec, c2c, chunks=None, seed=33, options=None):
+def run_yzx(shape, P, prec, c2c, chunks=None, seed=33, options=None, center=False):
     world = dfft.Comm.local(P) if P > 1 else None
     esz = 16 if prec == "double" else 8
     plans, ins, outs, host_ins = [], [], [], []
@@ -173,7 +178,10 @@ def run_yzx(shape, P, prec, c2c, chunks=None, seed=33, options=None):
             pl.setOption(k, v)
         pl.initFFT(dfft.GlobalSize(*shape), dfft.Slab_Partition(P), True, c2c=c2c)
         size, start = pl.getInSize(), pl.getInStart()
-        blk = orc.fill_block(shape, start, size, 2 if c2c else 1, seed=seed).astype(NPC[prec] if c2c else NPR[prec])
+        blk = orc.fill_block(shape, start, size, 2 if c2c else 1, seed=seed)
+        if center:
+            blk = blk - (CENTER * (1 + 1j) if c2c else CENTER)
+        blk = blk.astype(NPC[prec] if c2c else NPR[prec])
         plans.append(pl)
         host_ins.append(blk)
         ins.append(torch.from_numpy(blk).cuda())
@@ -209,6 +217,7 @@ def test_y_then_zx_vs_oracle(shape, P, c2c, prec):
         cover[o[1]:o[1] + s[1]] += 1
         assert np.max(np.abs(spec[r] - want[:, o[1]:o[1] + s[1], :])) / scale < TOL_FWD[prec]
     assert np.all(cover == 1)
+    check_forward_blocks(plans, spec, want, prec, int(np.prod(shape)), zero_mean=False)
 
 
 @pytest.mark.parametrize("chunks", [1, 2, 5])

@@ -13,6 +13,7 @@ torch = pytest.importorskip("torch")
 import distributedfft_amd as dfft  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 
+from parity_metric import check_forward_blocks  # noqa: E402
 from test_gpu_parity import NPDT, TOL_FWD, TOL_RT, rel, run_distributed, run_distributed_real  # noqa: E402
 
 OPT = {"spectral_layout": 1}
@@ -35,6 +36,7 @@ def test_x_contiguous_spectrum_c2c(shape, P1, P2, prec):
         # the same values as the reference layout holds (not bit for bit: the x pass may run another radix chain for its natural-line store)
         assert np.max(np.abs(spec[r] - spec_ref[r])) / scale < TOL_FWD[prec]
         assert rel(backs[r] / float(np.prod(shape)), ins[r]) < TOL_RT[prec]
+    check_forward_blocks(plans, spec, want, prec, g.size, zero_mean=False)
 
 
 @pytest.mark.parametrize("prec", ["double", "float"])
@@ -49,6 +51,7 @@ def test_x_contiguous_spectrum_r2c(shape, P1, P2, prec):
         s, o = pl.getOutSize(), pl.getOutStart()
         assert np.max(np.abs(spec[r] - want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]])) / scale < TOL_FWD[prec]
         assert rel(backs[r] / float(np.prod(shape)), ins[r]) < TOL_RT[prec]
+    check_forward_blocks(plans, spec, want, prec, g.size, zero_mean=False)
 
 
 @pytest.mark.parametrize("shape,P1,P2", [((32, 32, 32), 1, 1), ((32, 32, 32), 2, 4), ((64, 32, 16), 2, 2)])

@@ -19,6 +19,7 @@ torch = pytest.importorskip("torch")
 
 import distributedfft_amd as dfft  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
+from parity_metric import CENTER, check_forward, check_forward_blocks  # noqa: E402
 from test_gpu_parity import NPDT, rel, run_distributed, run_distributed_real  # noqa: E402
 import test_gpu_slab_sequences as slabs  # noqa: E402
 
@@ -26,24 +27,29 @@ FORCED = [4, 6, 8, 9, 15, 16, 21, 64, 100, 121, 256, 1000, 1024, 1155, 2048, 300
 LONG = [4098, 5000, 6000, 9999, 10000, 12288, 16384, 20000, 65536, 3 * 4093, 100000, 131072]
 
 
-def fft1d_case(N, prec, variant, batch, big_prime=False):
+def fft1d_case(N, prec, variant, batch, big_prime=False, label=None):
+    """the reference's distribution and the same centred (zero mean), both directions: the old bound scaled by max|X|, and per entry
+    (parity_metric.py; at fp32 asserted on the centred input).  `label`: rows of the parity table for this length"""
     rng = np.random.default_rng(N)
-    x = (rng.uniform(0, 255, (batch, N)) + 1j * rng.uniform(0, 255, (batch, N))).astype(NPDT[prec])
-    d_in = torch.from_numpy(x).cuda()
-    d_out = torch.zeros_like(d_in)
+    x0 = rng.uniform(0, 255, (batch, N)) + 1j * rng.uniform(0, 255, (batch, N))
     grow = max(1.0, np.log2(N) / 12.0)
-    for direction in (dfft.FORWARD, dfft.INVERSE):
-        torch.cuda.synchronize()
-        dfft.fft1d_batched(d_out, d_in, N, batch, direction, prec, variant=variant)
-        torch.cuda.synchronize()
-        ref = np.fft.fft(x.astype(np.complex128), axis=-1) if direction == dfft.FORWARD else np.fft.ifft(x.astype(np.complex128), axis=-1) * N
-        if big_prime:      # the oracle transforms a prime length as an O(N^2) sum (65537 points: 25 s per case): pocketfft alone here
-            want = ref
-        else:
-            want = orc.fft1d(x.astype(np.complex128), direction)
-            assert rel(want, ref) < 1e-12      # independent cross-check of the oracle itself on these lengths
-        assert rel(d_out.cpu().numpy(), want) < (2e-11 if prec == "double" else 2e-4) * grow
-    assert np.array_equal(d_in.cpu().numpy(), x), "the pass must not modify its input"
+    for centred, x in ((False, x0.astype(NPDT[prec])), (True, (x0 - CENTER * (1 + 1j)).astype(NPDT[prec]))):
+        d_in = torch.from_numpy(x).cuda()
+        d_out = torch.zeros_like(d_in)
+        for direction in (dfft.FORWARD, dfft.INVERSE):
+            torch.cuda.synchronize()
+            dfft.fft1d_batched(d_out, d_in, N, batch, direction, prec, variant=variant)
+            torch.cuda.synchronize()
+            ref = np.fft.fft(x.astype(np.complex128), axis=-1) if direction == dfft.FORWARD else np.fft.ifft(x.astype(np.complex128), axis=-1) * N
+            if big_prime:      # the oracle transforms a prime length as an O(N^2) sum (65537 points: 25 s per case): pocketfft alone here
+                want = ref
+            else:
+                want = orc.fft1d(x.astype(np.complex128), direction)
+                assert rel(want, ref) < 1e-12      # independent cross-check of the oracle itself on these lengths
+            check_forward(d_out.cpu().numpy(), want, prec, N, zero_mean=centred,
+                          label=f"{label} fft1d N={N} dir={direction} centred={centred}" if label else None)
+            assert rel(d_out.cpu().numpy(), want) < (2e-11 if prec == "double" else 2e-4) * grow
+        assert np.array_equal(d_in.cpu().numpy(), x), "the pass must not modify its input"
 
 
 @pytest.mark.parametrize("prec", ["double", "float"])
@@ -51,14 +57,14 @@ def fft1d_case(N, prec, variant, batch, big_prime=False):
 def test_fft1d_two_level_forced_vs_oracle(N, prec):
     """variant -2: two levels wherever the length splits -- plain x plain (64, 1024), plain x Bluestein (6, 3000),
     Bluestein x Bluestein (15, 121, 1155), sub-tile inner transforms (8192 = 4096 x 2 is avoided by the cost model, 6144 not)"""
-    fft1d_case(N, prec, -2, 45 if N < 4096 else 19)
+    fft1d_case(N, prec, -2, 45 if N < 4096 else 19, label="forced two-level" if N == FORCED[-1] else None)
 
 
 @pytest.mark.parametrize("prec", ["double", "float"])
 @pytest.mark.parametrize("N", LONG)
 def test_fft1d_long_lines_vs_oracle(N, prec):
     """lengths without a kernel of their own take the two-level form by themselves (ragged batch: not a multiple of the tile)"""
-    fft1d_case(N, prec, 0, 11 if N < 50000 else 5)
+    fft1d_case(N, prec, 0, 11 if N < 50000 else 5, label="long line" if N == LONG[-1] else None)
 
 
 LONG_BLUESTEIN = [4099, 8198, 5003, 10007, 12289, 2 * 3 * 4099, 65537]
@@ -72,7 +78,7 @@ def test_fft1d_long_bluestein_lines_vs_oracle(N, prec):
     lines themselves (four launches of the generic kernel, dfft.hip launch_long_bluestein).  The reference takes such sizes through
     cuFFT like any other (mpicufft_pencil_opt1.cpp:165-197)."""
     assert dfft.axis_plan_info(N, prec)["kind"] == "long_bluestein"
-    fft1d_case(N, prec, 0, 7 if N < 20000 else 3, big_prime=N > 20000)
+    fft1d_case(N, prec, 0, 7 if N < 20000 else 3, big_prime=N > 20000, label="long Bluestein" if N == LONG_BLUESTEIN[-1] else None)
 
 
 def test_every_length_has_a_plan_and_absurd_ones_fail_loudly():
@@ -92,6 +98,7 @@ def test_single_rank_long_bluestein_axes_vs_oracle(shape, c2c, prec):
     g, got, back = single(shape, prec, c2c)
     want = orc.fft3d_c2c(g.astype(np.complex128), -1) if c2c else orc.fft3d_r2c(g.astype(np.float64))
     assert rel(got, want) < (4e-11 if prec == "double" else 4e-4)
+    check_forward(got, want, prec, g.size, zero_mean=False)
     assert rel(back / g.size, g) < (2e-10 if prec == "double" else 1e-4)
 
 
@@ -113,9 +120,10 @@ def test_distributed_long_bluestein_axes_vs_oracle(shape, P1, P2, chunks, c2c):
         s, o = pl.getOutSize(), pl.getOutStart()
         assert np.max(np.abs(spec[r] - want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]])) / scale < 4e-11
         assert rel(backs[r] / float(np.prod(shape)), ins[r]) < 2e-10
+    check_forward_blocks(plans, spec, want, prec, g.size, zero_mean=False)
 
 
-def single(shape, prec, c2c, options=None, seed=5):
+def single(shape, prec, c2c, options=None, seed=5, center=False):
     cdt = torch.complex128 if prec == "double" else torch.complex64
     plan = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), precision=prec)
     for k, v in (options or {}).items():
@@ -123,6 +131,8 @@ def single(shape, prec, c2c, options=None, seed=5):
     plan.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(1, 1), True, c2c=c2c)
     esz = 16 if prec == "double" else 8
     g = orc.fill_block(shape, (0, 0, 0), shape, 2 if c2c else 1, seed=seed)
+    if center:
+        g = g - (CENTER * (1 + 1j) if c2c else CENTER)
     g = g.astype(NPDT[prec]) if c2c else g.astype(np.float64 if prec == "double" else np.float32)
     d_in = torch.from_numpy(g).cuda()
     d_out = torch.zeros(plan.getDomainSize() // esz, dtype=cdt, device="cuda")
@@ -153,6 +163,7 @@ def test_single_rank_long_axes_vs_oracle(shape, c2c, prec):
     g, got, back = single(shape, prec, c2c)
     want = orc.fft3d_c2c(g.astype(np.complex128), -1) if c2c else orc.fft3d_r2c(g.astype(np.float64))
     assert rel(got, want) < (4e-11 if prec == "double" else 4e-4)
+    check_forward(got, want, prec, g.size, zero_mean=False)
     assert rel(back / g.size, g) < (2e-10 if prec == "double" else 1e-4)
 
 
@@ -165,12 +176,14 @@ def test_single_rank_forced_two_level_vs_oracle(shape, c2c, prec):
     g, got, back = single(shape, prec, c2c, {"two_level": 1})
     want = orc.fft3d_c2c(g.astype(np.complex128), -1) if c2c else orc.fft3d_r2c(g.astype(np.float64))
     assert rel(got, want) < (2e-11 if prec == "double" else 2e-4)
+    check_forward(got, want, prec, g.size, zero_mean=False)
     assert rel(back / g.size, g) < (1e-10 if prec == "double" else 5e-5)
     _, plain, _ = single(shape, prec, c2c)
     assert rel(got, plain) < (2e-11 if prec == "double" else 2e-4)
     if c2c:
         g2, got2, back2 = single(shape, prec, c2c, {"two_level": 1, "single_order": 1})
         assert rel(got2, want) < (2e-11 if prec == "double" else 2e-4)
+        check_forward(got2, want, prec, g.size, zero_mean=False)
         assert rel(back2 / g.size, g) < (1e-10 if prec == "double" else 5e-5)
 
 
@@ -190,6 +203,7 @@ def test_distributed_forced_two_level_vs_oracle(shape, P1, P2, chunks, prec):
         ref = want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]]
         assert np.max(np.abs(spec[r] - ref)) / np.max(np.abs(want)) < tf
         assert rel(backs[r] / n3, ins[r]) < tr
+    check_forward_blocks(plans, spec, want, prec, int(n3), zero_mean=False)
     plans, ins, spec, backs = run_distributed_real(shape, P1, P2, prec, options=opts)
     rdt = np.float64 if prec == "double" else np.float32
     wantr = orc.fft3d_r2c(orc.fill_block(shape, (0, 0, 0), shape, 1, seed=13).astype(rdt).astype(np.float64))
@@ -198,6 +212,7 @@ def test_distributed_forced_two_level_vs_oracle(shape, P1, P2, chunks, prec):
         ref = wantr[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]]
         assert np.max(np.abs(spec[r] - ref)) / np.max(np.abs(wantr)) < tf
         assert rel(backs[r] / n3, ins[r]) < tr
+    check_forward_blocks(plans, spec, wantr, prec, int(n3), zero_mean=False)
 
 
 @pytest.mark.parametrize("shape,P1,P2", [((8200, 8, 6), 2, 2), ((6, 9000, 10), 2, 2), ((4, 6, 10000), 2, 2), ((16384, 4, 8), 4, 1)])
@@ -211,6 +226,7 @@ def test_distributed_long_axes_vs_oracle(shape, P1, P2):
         ref = want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]]
         assert np.max(np.abs(spec[r] - ref)) / np.max(np.abs(want)) < 4e-11
         assert rel(backs[r] / n3, ins[r]) < 2e-10
+    check_forward_blocks(plans, spec, want, "double", int(n3), zero_mean=False)
     plans, ins, spec, backs = run_distributed_real(shape, P1, P2, "double")
     wantr = orc.fft3d_r2c(orc.fill_block(shape, (0, 0, 0), shape, 1, seed=13))
     for r, pl in enumerate(plans):
@@ -218,6 +234,7 @@ def test_distributed_long_axes_vs_oracle(shape, P1, P2):
         ref = wantr[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]]
         assert np.max(np.abs(spec[r] - ref)) / np.max(np.abs(wantr)) < 4e-11
         assert rel(backs[r] / n3, ins[r]) < 2e-10
+    check_forward_blocks(plans, spec, wantr, "double", int(n3), zero_mean=False)
 
 
 @pytest.mark.parametrize("prec", ["double", "float"])
@@ -234,6 +251,7 @@ def test_slab_sequences_forced_two_level(shape, P, c2c, prec):
         s, o = pl.getOutSize(), pl.getOutStart()
         assert np.max(np.abs(spec[r] - want[:, :, o[2]:o[2] + s[2]])) / np.max(np.abs(want)) < tf
         assert np.max(np.abs(backs[r] / n3 - ins[r])) / 255.0 < tr
+    check_forward_blocks(plans, spec, want, prec, int(n3), zero_mean=False)
     plans, spec = slabs.run_yzx(shape, P, prec, c2c, options={"two_level": 1})
     g = slabs.global_input(shape, c2c, prec, seed=33)
     want = orc.fft3d_c2c(np.ascontiguousarray(g.astype(np.complex128)), -1)
@@ -241,6 +259,7 @@ def test_slab_sequences_forced_two_level(shape, P, c2c, prec):
     for r, pl in enumerate(plans):
         s, o = pl.getOutSize(), pl.getOutStart()
         assert np.max(np.abs(spec[r] - want[:, o[1]:o[1] + s[1], :])) / np.max(np.abs(want)) < tf
+    check_forward_blocks(plans, spec, want, prec, int(n3), zero_mean=False)
 
 
 def test_work_area_holds_the_level_scratch():
@@ -263,4 +282,6 @@ def test_work_area_holds_the_level_scratch():
     torch.cuda.synchronize()
     plan.execC2C(d_out, d_in, dfft.FORWARD)
     torch.cuda.synchronize()
-    assert rel(d_out.cpu().numpy().reshape(shape), orc.fft3d_c2c(g, -1)) < 4e-11
+    want = orc.fft3d_c2c(g, -1)
+    assert rel(d_out.cpu().numpy().reshape(shape), want) < 4e-11
+    check_forward(d_out.cpu().numpy().reshape(shape), want, "double", g.size, zero_mean=False)

@@ -14,7 +14,8 @@ torch = pytest.importorskip("torch")
 
 import distributedfft_amd as dfft  # noqa: E402,F401
 from oracle import oracle as orc  # noqa: E402
-from test_gpu_parity import NPDT, rel, run_distributed, run_distributed_real  # noqa: E402
+from parity_metric import CENTER, check_forward_blocks  # noqa: E402
+from test_gpu_parity import NPDT, NPR, rel, run_distributed, run_distributed_real  # noqa: E402
 
 VARIANTS = {"double": [1, 2, 3, 7, 8], "float": [1, 3, 4, 5, 6, 7, 9, 14, 15]}
 PASSES = ("fz", "fy", "fx", "ix", "iy", "iz")
@@ -23,24 +24,35 @@ TR = {"double": 1e-10, "float": 5e-5}
 
 
 @functools.lru_cache(maxsize=4)
-def spectrum(shape, prec, real):
+def real_field(shape, center):
+    """the global real input of run_distributed_real (seed 13), centred or not, before the cast to the plan's precision"""
+    return orc.fill_block(shape, (0, 0, 0), shape, 1, seed=13) - (CENTER if center else 0.0)
+
+
+@functools.lru_cache(maxsize=4)
+def spectrum(shape, prec, real, center=False):
     if real:
-        rdt = np.float64 if prec == "double" else np.float32
-        return orc.fft3d_r2c(orc.fill_block(shape, (0, 0, 0), shape, 1, seed=13).astype(rdt).astype(np.float64))
-    return orc.fft3d_c2c(orc.fill_block(shape, (0, 0, 0), shape, 2, seed=7).astype(NPDT[prec]).astype(np.complex128), -1)
+        return orc.fft3d_r2c(real_field(shape, center).astype(NPR[prec]).astype(np.float64))
+    g = orc.fill_block(shape, (0, 0, 0), shape, 2, seed=7) - (CENTER * (1 + 1j) if center else 0.0)
+    return orc.fft3d_c2c(g.astype(NPDT[prec]).astype(np.complex128), -1)
 
 
-def check(shape, P1, P2, prec, v, real):
+def check(shape, P1, P2, prec, v, real, center=False, label=None):
+    """center: the zero-mean input, where the per-entry bound is asserted at fp32 too (parity_metric.py)"""
     opts = {"variant_" + k: v for k in PASSES}
-    run = run_distributed_real if real else run_distributed
-    plans, ins, spec, backs = run(shape, P1, P2, prec, options=opts)
-    want = spectrum(shape, prec, real)
+    if real:
+        plans, ins, spec, backs = run_distributed_real(shape, P1, P2, prec, options=opts, field=real_field(shape, True) if center else None)
+    else:
+        plans, ins, spec, backs = run_distributed(shape, P1, P2, prec, options=opts, center=center)
+    want = spectrum(shape, prec, real, center)
     n3 = float(np.prod(shape))
+    per_entry = check_forward_blocks(plans, spec, want, prec, int(n3), zero_mean=center, label=label)
     for r, pl in enumerate(plans):
         s, o = pl.getOutSize(), pl.getOutStart()
         ref = want[:, o[1]:o[1] + s[1], o[2]:o[2] + s[2]]
         assert np.max(np.abs(spec[r] - ref)) / np.max(np.abs(want)) < TF[prec], (shape, P1, P2, v)
         assert rel(backs[r] / n3, ins[r]) < TR[prec], (shape, P1, P2, v)
+    return plans, ins, backs, per_entry
 
 
 @pytest.mark.parametrize("prec", ["double", "float"])
