@@ -37,7 +37,12 @@ class PassDesc(C.Structure):
 class ChainStep(C.Structure):
     _fields_ = [("group", C.c_char * 8), ("axis", C.c_int32), ("launches", C.c_int32), ("per_chunk", C.c_int32),
                 ("src", C.c_int32), ("dst", C.c_int32), ("conj", C.c_int32), ("form", C.c_int32), ("exchange", C.c_int32),
-                ("split", C.c_int32)]
+                ("split", C.c_int32), ("tables", C.c_int32)]
+
+
+class SpectralOp(C.Structure):
+    """dfft_spectral_op (include/dfft_c.h): the pointwise multiplier of dfft_exec_spectral_op"""
+    _fields_ = [("kind", C.c_int32), ("scale", C.c_double), ("mult", C.c_void_p), ("ax", C.c_void_p), ("ay", C.c_void_p), ("az", C.c_void_p)]
 
 
 class TraceOp(C.Structure):
@@ -75,6 +80,7 @@ SYMBOLS = [
     ("dfft_exec_c2c", _i, [_vp, _vp, _vp, _i]),
     ("dfft_enqueue_c2c", _i, [_vp, _vp, _vp, _i]),
     ("dfft_exec_dim", _i, [_vp, _vp, _vp, _i, _i]),
+    ("dfft_exec_spectral_op", _i, [_vp, _vp, _vp, C.POINTER(SpectralOp)]),
     ("dfft_get_in_size", _i, [_vp, _psz]),
     ("dfft_get_in_start", _i, [_vp, _psz]),
     ("dfft_get_out_size", _i, [_vp, _psz]),

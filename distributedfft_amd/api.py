@@ -22,6 +22,7 @@ from ._lib import Config, DfftError, check, lib
 Peer2Peer, All2All = 0, 1
 Sync, Streams, MPI_Type = 0, 1, 2
 FORWARD, INVERSE = -1, 1
+SPECTRAL_OP = 2      # DFFT_SPECTRAL_OP: the chain of execSpectralOp in debugChain / debugTrace
 
 
 class GlobalSize:
@@ -373,6 +374,25 @@ class MPIcuFFT:
             return
         f = lib().dfft_exec_c2c if sync else lib().dfft_enqueue_c2c
         check(f(self._h, _ptr(out), _ptr(in_), direction))
+
+    def execSpectralOp(self, out, in_, multiplier=None, tables=None, reciprocal=False, scale=1.0):
+        """out = IFFT(m * FFT(in_)), unnormalised, as one chain whose two x passes are a single kernel (dfft_exec_spectral_op; the plan
+        needs setOption("spectral_op", 1) before initFFT).  out and in_ are blocks of the input layout; in_ is only read.
+        multiplier: complex device array over the spectrum block in the plan's spectral layout (getOutStrides), m = scale * multiplier;
+        or tables = (ax, ay, az): real device tables with Nx, yo, zs entries, m = scale * (ax + ay + az) -- with reciprocal=True
+        m = scale / (ax + ay + az), 0 where the sum is 0"""
+        from ._lib import SpectralOp
+        if (multiplier is None) == (tables is None):
+            raise DfftError("execSpectralOp takes either multiplier= or tables=")
+        if multiplier is not None and reciprocal:
+            raise DfftError("reciprocal=True needs tables=")
+        val = lambda x: None if x is None else _ptr(x).value      # noqa: E731
+        if tables is not None:
+            ax, ay, az = tables
+            op = SpectralOp(2 if reciprocal else 1, float(scale), None, val(ax), val(ay), val(az))
+        else:
+            op = SpectralOp(0, float(scale), val(multiplier), None, None, None)
+        check(lib().dfft_exec_spectral_op(self._h, _ptr(out), _ptr(in_), C.byref(op)))
 
     def exchange(self, which, direction, sendbuf, recvbuf):
         """only the all-to-all of exchange `which` (1 row group / 2 column group)"""

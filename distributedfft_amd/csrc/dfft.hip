@@ -383,6 +383,24 @@ static int launch(dfft_plan *p, const Launch &L, int form, int axis, bool conj, 
     return 0;
 }
 
+// one launch of group xx (fft_spectral_kernel): forward x pass, the multiplier p->op, inverse x pass
+static int launch_spectral(dfft_plan *p, const Launch &L, const char *in, char *out, hipStream_t stream)
+{
+    if (L.args.ntiles == 0) return 0;
+    const dfft_spectral_op &op = p->op;
+    const size_t real = p->esz / 2;
+    PassArgs A = L.args;
+    A.in = in + L.in_off; A.out = out + L.out_off; A.tw = p->ax[2].tw; A.debug = 0;
+    fill_tables(p, L, A);
+    A.mkind = op.kind; A.mscale = op.scale;
+    if (op.kind == 0) A.mult = static_cast<const char *>(op.mult) + L.mult_off * p->esz;
+    else { A.mtx = op.ax; A.mty = static_cast<const char *>(op.ay) + L.ty_off * real; A.mtz = op.az; }
+    const int r = p->prec == DFFT_F64 ? launch_spectral_f64((int)p->Nx, A, stream) : launch_spectral_f32((int)p->Nx, A, stream);
+    if (r == -1) return fail(ERR_UNSUPPORTED, "spectral_op: unsupported x length " + std::to_string(p->Nx));
+    if (r != 0) return fail(r, std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)r));
+    return 0;
+}
+
 // `ready`: an event recorded when the send data was complete (the producer kernel of this pipeline chunk), if the caller has one:
 // the relay orders its first hop after it instead of after everything on `stream` (comm.hpp)
 static int exchange_tables(dfft_plan *p, int which, const A2A &T, bool forward, const char *send, char *recv,
@@ -465,6 +483,7 @@ static hipEvent_t pipe_event(dfft_plan *p, size_t i)
 static const Chain &chain_of(const dfft_plan *p, int direction, int dims)
 {
     const Pipeline &pl = p->pl;
+    if (direction == DFFT_SPECTRAL_OP) return pl.spec;      // (dfft_exec_spectral_op; empty without option spectral_op)
     const bool fwd = direction != DFFT_INVERSE;
     if (dims == 3 && one_rank_alternative(p) && !(fwd ? pl.one_fwd : pl.one_inv).steps.empty()) return fwd ? pl.one_fwd : pl.one_inv;
     return fwd ? pl.fwd[dims - 1] : pl.inv[dims - 1];
@@ -562,13 +581,15 @@ struct HipSink {
         const Step &t = st[(size_t)step];
         const Group &g = p->pl.groups[t.group];
         if (log) log->push_back(trace_launch(p, st, step, chunk, k, s));
+        if (t.group == G_XX) return launch_spectral(p, g.L[(size_t)k], buf(t.src), buf(t.dst), S[s]);
         return launch(p, g.L[(size_t)k], t.form, g.axis, t.conj, buf(t.src), buf(t.dst), S[s]);
     }
     int xchg(int step, int chunk, int s, int ready)
     {
         const Step &t = st[(size_t)step];
         const Pipeline &pl = p->pl;
-        const std::vector<A2A> &T = direction == DFFT_INVERSE ? (t.xchg == 1 ? pl.i1 : pl.i2) : (t.xchg == 1 ? pl.f1 : pl.f2);
+        const int dir = t.tables ? t.tables : direction;
+        const std::vector<A2A> &T = dir == DFFT_INVERSE ? (t.xchg == 1 ? pl.i1 : pl.i2) : (t.xchg == 1 ? pl.f1 : pl.f2);
         if (log) log->push_back(trace_exchange(st, step, chunk, s));
         return exchange_tables(p, t.xchg, T[(size_t)chunk], true, buf(t.dst), buf(st[(size_t)step + 1].src), S[s], s == S_COMM2 ? 1 : 0, 0,
                                pl.ev[(size_t)ready]);      // (tables in send / receive order)
@@ -660,15 +681,19 @@ template <typename Sink> static int schedule_chain(const dfft_plan *p, const Cha
     return 0;
 }
 
+static int trace_slot(int direction) { return direction == DFFT_SPECTRAL_OP ? 2 : direction == DFFT_INVERSE ? 1 : 0; }
+
 // Runs one execution chain: schedule_chain through the sink that issues HIP calls
 static int run_chain(dfft_plan *p, int direction, int dims, void *out, const void *in)
 {
     const Chain &ch = chain_of(p, direction, dims);
-    if (ch.steps.empty()) return fail(ERR_UNSUPPORTED, "the Y_Then_ZX sequence is forward only (as in the reference)");
+    if (ch.steps.empty())
+        return direction == DFFT_SPECTRAL_OP ? fail(ERR_STATE, "plan was initialised without option spectral_op")
+                                             : fail(ERR_UNSUPPORTED, "the Y_Then_ZX sequence is forward only (as in the reference)");
     const StreamUse use = streams_of(p, ch);
     p->nspans = 0; p->last_dir = direction == DFFT_INVERSE ? DFFT_INVERSE : DFFT_FORWARD;
     std::vector<dfft_trace_op> *log = nullptr;
-    if (p->opt.trace) { log = &p->trace_log[direction == DFFT_INVERSE ? 1 : 0]; log->clear(); }
+    if (p->opt.trace) { log = &p->trace_log[trace_slot(direction)]; log->clear(); }
     HipSink sk{p, ch.steps, direction, out, in, log, {}};
     TRY(sk.open(use));
     return schedule_chain(p, ch, use, sk);
@@ -885,6 +910,7 @@ static int *option_slot(Options &o, const std::string &k)
     if (k == "native_mixed") return &o.native_mixed;
     if (k == "graph") return &o.graph;
     if (k == "spectral_layout") return &o.spectral;
+    if (k == "spectral_op") return &o.spectral_op;
     if (k == "compute_streams") return &o.compute_streams;
     if (k == "trace") return &o.trace;
     for (int i = 0; i < 6; i++) {
@@ -1041,6 +1067,16 @@ int dfft_init(dfft_plan *p, size_t Nx, size_t Ny, size_t Nz, int P1, int P2, int
     }
     if (p->opt.spectral && (zyx || yzx)) return fail(ERR_UNSUPPORTED, "spectral_layout: pencil and default slab plans only (not the Z_Then_YX / Y_Then_ZX sequences)");
     if (p->opt.spectral && p->opt.spectral != 1) return fail(ERR_ARG, "spectral_layout: 0 = the reference's [Nx][yo][zs], 1 = x-contiguous [yo][zs][Nx]");
+    if (p->opt.spectral_op) {
+        if (zyx || yzx) return fail(ERR_UNSUPPORTED, "spectral_op: pencil and default slab plans only (not the Z_Then_YX / Y_Then_ZX sequences)");
+        if (p->opt.spectral_op != 1) return fail(ERR_ARG, "spectral_op: 0 or 1");
+        // the fused x pass has the default configuration of the powers of two 2 .. 2048 (csrc/spectral_*.hip); no unfused fallback
+        const Axis &ax = p->ax[2];
+        if (ax.bluestein || !is_pow2(Nx) || !(p->prec == DFFT_F64 ? spectral_supported_f64((int)Nx) : spectral_supported_f32((int)Nx)))
+            return fail(ERR_UNSUPPORTED, "spectral_op: an x length of " + std::to_string(Nx) + " points has no fused forward-multiply-inverse kernel "
+                                         "(powers of two from 2 to 2048 on a native chain)");
+        p->worksize_d += p->domainsize;      // the slice that stands in for `out` (forward half) and `in` (inverse half)
+    }
     // (one rank: the inverse of an x-contiguous spectrum cannot be the forward launches with conjugation -- their input is the natural grid)
     p->spectral_mirror = p->opt.spectral && p->nranks == 1;
     TRY(zyx ? build_pipeline_zyx(p, p->pl) : yzx ? build_pipeline_yzx(p, p->pl) : build_pipeline(p, p->pl));
@@ -1209,7 +1245,7 @@ static int ensure_device_state(dfft_plan *p)
         p->stream_owned = true;
     }
     // the streams the whole transform needs as the options stand (an exec creates what it needs beyond them: HipSink::open)
-    for (const Chain *ch : {&chain_of(p, DFFT_FORWARD, 3), &chain_of(p, DFFT_INVERSE, 3)}) {
+    for (const Chain *ch : {&chain_of(p, DFFT_FORWARD, 3), &chain_of(p, DFFT_INVERSE, 3), &chain_of(p, DFFT_SPECTRAL_OP, 3)}) {
         HipSink sk{p, ch->steps, DFFT_FORWARD, nullptr, nullptr, nullptr, {}};
         TRY(sk.open(streams_of(p, *ch)));
     }
@@ -1316,6 +1352,29 @@ int dfft_exec_c2r(dfft_plan *p, void *out, void *in)
     if (p->c2c) return fail(ERR_STATE, "plan was initialised for C2C");
     if (!out || !in) return fail(ERR_ARG, "null buffer");
     TRY(run_graphed(p, 3, in, out, [&]() { return run_chain(p, DFFT_INVERSE, 3, out, in); }));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int dfft_exec_spectral_op(dfft_plan *p, void *out, const void *in, const dfft_spectral_op *op)
+{
+    if (p && p->initialized && p->pl.spec.steps.empty())
+        return fail(ERR_STATE, "plan was initialised without option spectral_op (set it before dfft_init)");
+    TRY(check_ready(p));
+    if (!out || !in || !op) return fail(ERR_ARG, "null buffer or operator");
+    if (out == in) return fail(ERR_ARG, "spectral_op: out == in is not supported");
+    if (op->kind < 0 || op->kind > 2) return fail(ERR_ARG, "spectral_op: kind must be 0 (array), 1 (sum of tables) or 2 (reciprocal of the sum)");
+    if (op->kind == 0 ? !op->mult : (!op->ax || !op->ay || !op->az)) return fail(ERR_ARG, "spectral_op: null multiplier");
+    if (op->kind == 0) {
+        // one tile per workgroup: the kernel adds 32-bit lane offsets (t*MK + l*ME elements) to a scalar base per point
+        PassInfo pi;
+        const Launch *L = p->pl.groups[G_XX].L.empty() ? nullptr : &p->pl.groups[G_XX].L[0];
+        if (L && pass_info(p->prec, (int)p->Nx, &pi) && pi.G == 1 &&
+            ((uint64_t)(pi.N / pi.E) * L->args.MK + (uint64_t)pi.TL * L->args.ME) * p->esz >= (1ull << 32))
+            return fail(ERR_UNSUPPORTED, "spectral_op: the multiplier block is too large for the kernel's 32-bit lane offsets");
+    }
+    p->op = *op;
+    TRY(run_chain(p, DFFT_SPECTRAL_OP, 3, out, in));
     HIP_TRY(hipStreamSynchronize(p->stream));
     return 0;
 }
@@ -1441,7 +1500,8 @@ int dfft_debug_get_pass(const dfft_plan *p, const char *name, int index, dfft_pa
 int dfft_debug_get_chain(const dfft_plan *p, int direction, int dims, dfft_chain_step *steps, int capacity, int *count)
 {
     if (!p || !p->initialized) return fail(ERR_STATE, "plan not initialised");
-    if (dims < 1 || dims > 3 || (direction != DFFT_FORWARD && direction != DFFT_INVERSE)) return fail(ERR_ARG, "bad direction or dims");
+    const bool spec = direction == DFFT_SPECTRAL_OP && dims == 3;
+    if (dims < 1 || dims > 3 || (direction != DFFT_FORWARD && direction != DFFT_INVERSE && !spec)) return fail(ERR_ARG, "bad direction or dims");
     const Chain &ch = chain_of(p, direction, dims);
     const std::vector<Step> &st = ch.steps;
     if (count) *count = (int)st.size();
@@ -1453,6 +1513,7 @@ int dfft_debug_get_chain(const dfft_plan *p, int direction, int dims, dfft_chain
         strncpy(d.group, g.name, sizeof(d.group) - 1);
         d.axis = g.axis; d.launches = (int32_t)g.L.size(); d.per_chunk = s.per_chunk;
         d.src = s.src; d.dst = s.dst; d.conj = s.conj; d.form = s.form; d.exchange = s.xchg; d.split = ch.split;
+        d.tables = s.tables ? s.tables : (direction == DFFT_INVERSE ? DFFT_INVERSE : DFFT_FORWARD);
     }
     return 0;
 }
@@ -1460,14 +1521,15 @@ int dfft_debug_get_chain(const dfft_plan *p, int direction, int dims, dfft_chain
 int dfft_debug_trace_chain(const dfft_plan *p, int direction, int dims, dfft_trace_op *ops, int capacity, int *count)
 {
     if (!p || !p->initialized) return fail(ERR_STATE, "plan not initialised");
-    if (dims < 0 || dims > 3 || (direction != DFFT_FORWARD && direction != DFFT_INVERSE)) return fail(ERR_ARG, "bad direction or dims");
+    const bool spec = direction == DFFT_SPECTRAL_OP && (dims == 3 || dims == 0);
+    if (dims < 0 || dims > 3 || (direction != DFFT_FORWARD && direction != DFFT_INVERSE && !spec)) return fail(ERR_ARG, "bad direction or dims");
     std::vector<dfft_trace_op> dry;
     if (dims > 0) {
         const Chain &ch = chain_of(p, direction, dims);
         DrySink sk{p, ch.steps, dry};
         TRY(schedule_chain(p, ch, streams_of(p, ch), sk));
     }
-    const std::vector<dfft_trace_op> &v = dims > 0 ? dry : p->trace_log[direction == DFFT_INVERSE ? 1 : 0];
+    const std::vector<dfft_trace_op> &v = dims > 0 ? dry : p->trace_log[trace_slot(direction)];
     if (count) *count = (int)v.size();
     for (size_t i = 0; i < v.size() && (int)i < capacity; i++) ops[i] = v[i];
     return 0;

@@ -44,6 +44,11 @@ bool real_supported_f32(int M);
 int launch_bluestein_f64(int M, const PassArgs &A, hipStream_t stream);
 int launch_bluestein_f32(int M, const PassArgs &A, hipStream_t stream);
 bool pass_info_f32(int N, int variant, PassInfo *pi);
+// fused forward-multiply-inverse x pass (fft_spectral_kernel): powers of two 2 .. 2048, the default configuration of the length
+int launch_spectral_f64(int N, const PassArgs &A, hipStream_t stream);
+int launch_spectral_f32(int N, const PassArgs &A, hipStream_t stream);
+bool spectral_supported_f64(int N);
+bool spectral_supported_f32(int N);
 #ifdef DFFT_EXPERIMENTS
 int launch_shfl_f32(int N, int dpp, const PassArgs &A, hipStream_t stream);      // LDS-free shuffle pass (A/B only)
 #endif

@@ -120,6 +120,16 @@ struct PassArgs {
     int32_t lb;
     uint32_t lbL, lbK;
     const void *lbtab;
+    // fft_spectral_kernel only: the pointwise multiplier between its forward and its inverse transform (dfft_spectral_op).
+    // Point k of line (a, e = b*TL + l) is multiplied by
+    //   mkind 0: mscale * mult[k*MK + a*MA + e*ME]                 (complex array in the layout of the plan's spectrum block)
+    //   mkind 1: mscale * (mtx[k] + mty[a] + mtz[e])               (three real tables)
+    //   mkind 2: mscale / (mtx[k] + mty[a] + mtz[e]), 0 where the sum is 0
+    int32_t mkind;
+    double mscale;
+    const void *mult;
+    uint64_t MK, MA, ME;
+    const void *mtx, *mty, *mtz;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -451,7 +461,8 @@ template <typename Cfg, int RP, int I, int JM> __host__ __device__ __forceinline
 
 // twiddle + butterflies of one Stockham pass: radix RP, previous sub-transform length NS; JM = 1: conjugate-pair
 // assignment of the butterflies (pair_j)
-template <typename Cfg, int RP, int NS, int JM = 0>
+template <typename C> __device__ __forceinline__ void sched_fence(C &x) { asm volatile("" : "+v"(x)); }
+template <typename Cfg, int RP, int NS, int JM = 0, int SEQ = 0>
 __host__ __device__ __forceinline__ void pass_compute(typename Cfg::C *v, int t, const typename Cfg::C *__restrict__ W)
 {
     using C = typename Cfg::C;
@@ -489,6 +500,11 @@ __host__ __device__ __forceinline__ void pass_compute(typename Cfg::C *v, int t,
             }
         }
         Dif<RP, i, S, C>::run(v);
+#if defined(__HIP_DEVICE_COMPILE__)
+        // SEQ: the butterflies of a thread one after the other (a scheduling fence on the outputs of each)
+        if constexpr (SEQ != 0 && S > 1)
+            static_for<0, RP>([&](auto mc) { constexpr int m = decltype(mc)::value; sched_fence(v[i + m * S]); });
+#endif
     });
 }
 
@@ -626,28 +642,28 @@ __device__ __forceinline__ void exchange(typename Cfg::C *v, typename Cfg::real 
 // pass; (t2, lw2): coordinates from the first exchange on (identical unless MAP == 2)
 // PAIR = 1: the LAST pass has the conjugate-pair butterfly assignment (R2C: split in registers afterwards);
 // PAIR = 2: the FIRST pass has it (C2R: merge in registers before)
-template <typename Cfg, int PAIR = 0>
+template <typename Cfg, int PAIR = 0, int SEQ = 0>
 __device__ __forceinline__ void transform(typename Cfg::C *v, typename Cfg::real *lds,
                                           const typename Cfg::C *__restrict__ W, int t, int lw, int t2, int lw2)
 {
     constexpr int R1 = Cfg::r1, R2 = Cfg::r2, R3 = Cfg::r3, R4 = Cfg::r4, NP = Cfg::NPASS;
     static_assert(PAIR == 0 || NP >= 2, "paired butterflies need at least two passes");
     constexpr int JS1 = PAIR == 2;
-    pass_compute<Cfg, R1, 1>(v, t, W);
+    pass_compute<Cfg, R1, 1, 0, SEQ>(v, t, W);
     if constexpr (R2 > 1) {
         constexpr int L = PAIR == 1 && NP == 2;
         exchange<Cfg, R1, 1, JS1, L, R2>(v, lds, t, lw, t2, lw2, true);
-        pass_compute<Cfg, R2, R1, L>(v, t2, W);
+        pass_compute<Cfg, R2, R1, L, SEQ>(v, t2, W);
     }
     if constexpr (R3 > 1) {
         constexpr int L = PAIR == 1 && NP == 3;
         exchange<Cfg, R2, R1, 0, L, R3>(v, lds, t2, lw2, t2, lw2, false);
-        pass_compute<Cfg, R3, R1 * R2, L>(v, t2, W);
+        pass_compute<Cfg, R3, R1 * R2, L, SEQ>(v, t2, W);
     }
     if constexpr (R4 > 1) {
         constexpr int L = PAIR == 1 && NP == 4;
         exchange<Cfg, R3, R1 * R2, 0, L, R4>(v, lds, t2, lw2, t2, lw2, false);
-        pass_compute<Cfg, R4, R1 * R2 * R3, L>(v, t2, W);
+        pass_compute<Cfg, R4, R1 * R2 * R3, L, SEQ>(v, t2, W);
     }
 }
 // line-fastest kernels (r2c / c2r / Bluestein): one coordinate set
@@ -1082,6 +1098,140 @@ __global__ __launch_bounds__(Cfg::THREADS) void fft_pass_kernel(const PassArgs A
             if constexpr (Cfg::NPASS > 1) __syncthreads();      // the next tile's first scatter reuses the LDS plane
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// Spectral operator on complete x lines: forward transform, pointwise multiplier, inverse transform in ONE launch
+// (dfft_exec_spectral_op: the forward -> pointwise -> inverse loop of the reference's testcase 4,
+// tests/src/pencil/random_dist_3D.cu:685-811).  The load side is that of the forward x pass (tiled blocks of exchange 2), the
+// store side that of the inverse x pass (same-tile blocks for exchange 2 backwards); the spectrum never reaches memory.
+//
+// The hand-off between the two chains is a renaming of registers.  After transform<Cfg>() register c of thread t2 holds
+// output point t2 + NT*sigma(c), sigma(c) = (c % S) + brev(c / S, RLAST)*S with S = E / RLAST (the k0 of store_tile); the
+// first pass of a chain expects register c' to hold point t + NT*c'.  So the thread already owns the points of its second
+// transform: w[sigma(c)] = v[c] * m(t2 + NT*sigma(c)), every index a compile-time constant.  The second chain and the store
+// run in the coordinates (t2, lw2) of the first chain's later passes.
+// The inverse transform is conj(forward(conj(y))): the first conjugation is folded into the product, the second is one
+// sign flip before the store.  The result is unnormalised (N * ifft), like every inverse pass; PassArgs::mscale carries
+// whatever factor the caller wants.
+// The multiplier values are fetched after the first chain, CH registers at a time: ahead of it they would have to live
+// through the chain next to the data (E more complex registers: the 1024-point fp64 configuration would leave its 128 VGPRs).
+// ------------------------------------------------------------------------------------------
+template <typename Cfg> constexpr int spectral_sigma(int c)
+{
+    constexpr int S = Cfg::kE / Cfg::RLAST;
+    return (c % S) + brev(c / S, Cfg::RLAST) * S;
+}
+
+// waves per SIMD that the LDS of a configuration leaves room for (160 KiB per CU, four SIMDs) where the LDS is what bounds the
+// occupancy; the kernel is compiled for that many (1024 fp64 points: two workgroups of 512 threads per CU, 128 VGPRs, like the pass kernel)
+template <typename Cfg> constexpr int spectral_waves()
+{
+    if (Cfg::LDS_BYTES <= 48 * 1024) return 1;
+    const int w = (int)((160 * 1024) / Cfg::LDS_BYTES) * ((Cfg::THREADS + 63) / 64) / 4;
+    return w < 1 ? 1 : w > 4 ? 4 : w;
+}
+
+// TABLES: 0 = the multiplier is a complex array (PassArgs::mkind 0), 1 = it is built from three real tables (mkind 1, 2).  Two
+// instantiations, not a branch: with both forms in one kernel the transformed registers flow through either and the 1024-point fp64
+// configuration takes 152 VGPRs instead of 128, the 2048-point one spills
+template <typename Cfg, int TABLES>
+__global__ __launch_bounds__(Cfg::THREADS, spectral_waves<Cfg>()) void fft_spectral_kernel(const PassArgs A)
+{
+    using C = typename Cfg::C;
+    using R = typename Cfg::real;
+    constexpr int E = Cfg::kE, NT = Cfg::NT;
+    static_assert(Cfg::kSUB == 1 && !Cfg::kPERSIST && Cfg::kFIX == 0, "whole tiles, one tile walk, every address form");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    R *lds = reinterpret_cast<R *>(smem);
+
+    const int tid = threadIdx.x;
+    int lw, t, lw2, t2;
+    thread_map<Cfg, Cfg::PF_FIRST>(tid, lw, t);
+    thread_map<Cfg, Cfg::PF_REST>(tid, lw2, t2);
+
+    const C *__restrict__ in = reinterpret_cast<const C *>(A.in);
+    C *__restrict__ out = reinterpret_cast<C *>(A.out);
+    const C *__restrict__ W = reinterpret_cast<const C *>(A.tw);
+
+    const uint32_t blk = logical_block<>(A, blockIdx.x, gridDim.x);
+    C v[E];
+    load_tile<Cfg>(A, in, tile_pos<Cfg>(A, blk, lw), t, v);
+    transform<Cfg, 0, 1>(v, lds, W, t, lw, t2, lw2);
+
+    // (the tile position is worked out again from a value the compiler cannot see through, here and for the store: kept from the
+    // load, its six registers would live through the first chain -- see the second chain below)
+    int lwm = lw2;
+    asm volatile("" : "+v"(lwm));
+    const TilePos<Cfg::kTL> P = tile_pos<Cfg>(A, blk, lwm);
+    const R scale = (R)A.mscale;
+    C w[E];
+    constexpr int CH = E >= 8 ? 4 : E;
+    // a chunk's products are complete before the next chunk's multiplier loads are issued: left to itself the compiler issues all E
+    // loads at once (160 VGPRs at 1024 fp64 points, scratch at 2048)
+    auto settle = [](C &x) { asm volatile("" : "+v"(x) : : "memory"); };
+    // ... and the first chunk's loads stay behind the first chain's last butterflies, where the twiddles are live as well
+    static_for<0, E>([&](auto cc) { settle(v[decltype(cc)::value]); });
+    if constexpr (!TABLES) {
+        // G == 1: the tile (a, b) is the same in every lane, so tile and point make a scalar base and the lane adds 32-bit
+        // (t2*MK + l*ME) bytes (as load_tile does; the host checks the range); else per-lane 64-bit addresses.  A lane without a line
+        // (a ragged tile; its data are zeros) reads the multiplier of the tile's first line: no branch around the loads
+        const char *ub = reinterpret_cast<const char *>(A.mult);
+        uint32_t lane = 0;
+        if constexpr (Cfg::kG == 1) {
+            const uint32_t au = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.a), bu = (uint32_t)__builtin_amdgcn_readfirstlane((int)P.b);
+            ub += ((uint64_t)au * A.MA + (uint64_t)bu * Cfg::kTL * A.ME) * sizeof(C);
+            lane = (uint32_t)(((uint64_t)t2 * A.MK + (uint64_t)(P.ok ? P.l : 0) * A.ME) * sizeof(C));
+        } else {
+            ub += ((uint64_t)P.a * A.MA + (uint64_t)(P.ok ? P.e : 0) * A.ME + (uint64_t)t2 * A.MK) * sizeof(C);
+        }
+        static_for<0, E / CH>([&](auto qq) {
+            constexpr int q = decltype(qq)::value;
+            C m[CH];
+            static_for<0, CH>([&](auto jj) {
+                constexpr int j = decltype(jj)::value, s = spectral_sigma<Cfg>(q * CH + j);
+                m[j] = stream_load<Cfg>(reinterpret_cast<const C *>(ub + (uint64_t)(NT * s) * A.MK * sizeof(C) + lane));
+            });
+            static_for<0, CH>([&](auto jj) {
+                constexpr int j = decltype(jj)::value, c = q * CH + j, s = spectral_sigma<Cfg>(c);
+                const C y = cmul2(v[c], m[j], ci(m[j])) * scale;
+                w[s].x = y.x; w[s].y = -y.y;
+                settle(w[s]);
+            });
+        });
+    } else {
+        const R *tx = reinterpret_cast<const R *>(A.mtx) + t2;
+        const R sy = P.ok ? reinterpret_cast<const R *>(A.mty)[P.a] : (R)0, sz = P.ok ? reinterpret_cast<const R *>(A.mtz)[P.e] : (R)0;
+        const bool recip = A.mkind == 2;
+        static_for<0, E / CH>([&](auto qq) {
+            constexpr int q = decltype(qq)::value;
+            R m[CH];
+            static_for<0, CH>([&](auto jj) {
+                constexpr int j = decltype(jj)::value, s = spectral_sigma<Cfg>(q * CH + j);
+                m[j] = tx[NT * s];
+            });
+            static_for<0, CH>([&](auto jj) {
+                constexpr int j = decltype(jj)::value, c = q * CH + j, s = spectral_sigma<Cfg>(c);
+                const R sum = (m[j] + sy) + sz;
+                const R f = recip ? (sum != (R)0 ? scale / sum : (R)0) : scale * sum;
+                w[s].x = v[c].x * f; w[s].y = -(v[c].y * f);
+                settle(w[s]);
+            });
+        });
+    }
+    // the second chain's first exchange skips its leading barrier, and the plane is still being gathered from by the first chain
+    if constexpr (Cfg::NPASS > 1) __syncthreads();
+    // The second chain starts from values the compiler cannot see through -- the same twiddle table, the same thread coordinates.
+    // It would otherwise keep every twiddle, LDS address and table index of the first chain in registers for the second one
+    // (512 fp64 points: 190 VGPRs instead of 100; fp32 1024 / 2048 points: scratch); recomputing them is a few integer operations.
+    const C *W2 = W;
+    int t3 = t2, lw3 = lw2;
+    asm volatile("" : "+s"(W2), "+v"(t3), "+v"(lw3));
+    transform<Cfg, 0, 1>(w, lds, W2, t3, lw3, t3, lw3);
+    static_for<0, E>([&](auto cc) { constexpr int c = decltype(cc)::value; w[c].y = -w[c].y; });
+    int t4 = t3, lw4 = lw3;      // (and the store's addresses are worked out after the second chain, not before it)
+    asm volatile("" : "+v"(t4), "+v"(lw4));
+    store_tile<Cfg>(A, out, tile_pos<Cfg>(A, blk, lw4), t4, w);
 }
 
 // ------------------------------------------------------------------------------------------

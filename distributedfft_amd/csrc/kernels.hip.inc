@@ -37,6 +37,26 @@ template <typename Cfg> static int launch_cfg(const PassArgs &A, hipStream_t str
     return (int)hipGetLastError();
 }
 
+// fft_spectral_kernel (forward transform, pointwise multiplier, inverse transform of complete x lines in one launch): whole tiles,
+// one workgroup per G tiles, the dynamic-LDS attribute as for launch_cfg.  TABLES = the part of spectral_<p>.hip (-DDFFT_PART):
+// 0 array multiplier, 1 table multiplier
+template <typename Cfg, int TABLES> static int launch_spectral_cfg(const PassArgs &A, hipStream_t stream)
+{
+    static bool attr_set = false;
+    if (!attr_set && Cfg::LDS_BYTES > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&fft_spectral_kernel<Cfg, TABLES>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
+        if (e != hipSuccess) return (int)e;
+        attr_set = true;
+    }
+    const uint32_t grid = (A.ntiles + Cfg::kG - 1) / Cfg::kG;
+    if (grid == 0) return 0;
+    hipLaunchKernelGGL((fft_spectral_kernel<Cfg, TABLES>), dim3(grid), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, A);
+    return (int)hipGetLastError();
+}
+#define DFFT_CASE_SPECTRAL(n, v, cfg) case n: return launch_spectral_cfg<cfg, DFFT_PART>(A, stream);
+#define DFFT_CASE_SPECTRAL_OK(n, v, cfg) case n: return true;
+
 // MODE 1 = R2C (ONEPLANE: 0 two-plane split through LDS, 1 one-plane split, 2 split in registers with the conjugate-pair
 // butterfly assignment), MODE 3 = R2C on strided real lines, MODE 2 = C2R (ONEPLANE 2: merge in registers)
 template <typename Cfg, int MODE, int ONEPLANE> struct RealKernel;

@@ -61,7 +61,7 @@ static std::vector<Launch> &group(Pipeline &pl, int g, size_t n)
 static void clear(Pipeline &pl)
 {
     for (auto &g : pl.groups) g.L.clear();
-    for (Chain *c : {&pl.fwd[0], &pl.fwd[1], &pl.fwd[2], &pl.inv[0], &pl.inv[1], &pl.inv[2], &pl.one_fwd, &pl.one_inv}) *c = Chain();
+    for (Chain *c : {&pl.fwd[0], &pl.fwd[1], &pl.fwd[2], &pl.inv[0], &pl.inv[1], &pl.inv[2], &pl.one_fwd, &pl.one_inv, &pl.spec}) *c = Chain();
     pl.single = false;
 }
 
@@ -228,6 +228,24 @@ int build_pipeline(dfft_plan *p, Pipeline &pl)
             L.out_off = x0[c] * ys * zline_bytes;
         }
     }
+    // ---------------- spectral operator (option spectral_op): forward x, multiplier, inverse x in one launch per ky chunk ----------------
+    if (p->opt.spectral_op) {
+        auto &xx = group(pl, G_XX, C);
+        for (int c = 0; c < C; c++) {
+            Launch &L = xx[c];
+            // lines (ky in the chunk, kz'): the load side of fx on those rows -- a row of a (peer, chunk) block holds len*zs elements, so
+            // the chunk's first row k0[c] moves every block base by k0[c]*len*zs -- and the store side of ix[c]
+            L.args = base(kl[c], zs, LOAD_TILED, STORE_TILED_SAME, 0);
+            L.lseg = fx.lseg;
+            for (int s = 0; s < L.lseg.nseg; s++) L.lseg.base[s] += (uint64_t)k0[c] * L.lseg.len[s] * zs;
+            L.sseg = ix[c].sseg;
+            L.args.LA = (uint32_t)kl[c];
+            // the multiplier array is addressed like the spectrum block ix[c] loads (dfft_get_out_strides), the chunk's rows first
+            if (p->opt.spectral) { L.args.MK = 1; L.args.MA = (uint64_t)zs * Nx; L.args.ME = Nx; L.mult_off = k0[c] * zs * Nx; }
+            else { L.args.MK = (uint64_t)yo * zs; L.args.MA = zs; L.args.ME = 1; L.mult_off = k0[c] * zs; }
+            L.ty_off = k0[c];
+        }
+    }
     // ---------------- partial transforms (d = 1, 2) ----------------
     group(pl, G_PZ1, 1)[0].args = base(xs, ys, LOAD_LINES, STORE_LINES, 0);
     group(pl, G_QZ1, 1)[0].args = base(xs, ys, LOAD_LINES, STORE_LINES, 1);
@@ -266,6 +284,25 @@ int build_pipeline(dfft_plan *p, Pipeline &pl)
         pl.inv[2].steps = {{G_IX, FORM_INV, BUF_IN, 0, 0, x2}, {G_IY, FORM_INV, ysrc, BUF_IN, 2, x1, true}, {G_IZ, zi, zsrc, BUF_OUT, 4, 0, P2 == 1}};
     }
     pl.fwd[2].split = pl.inv[2].split = true;
+    if (p->opt.spectral_op) {
+        // forward half as fwd[2], inverse half as inv[2], with one more work slice E in the place of `out` (forward) and `in` (inverse):
+        //   z: in -> E   [ex1: E -> W0]   y: -> ydst   [ex2: -> xsrc]   xx: xsrc -> xd   [ex2^-1: xd -> isrc]   y^-1: isrc -> idst
+        //   [ex1^-1: idst -> zsrc]   z^-1: -> out
+        // xx needs complete x lines (every chunk of exchange 2) and y^-1 complete ky lines.  A slice is written again only behind a
+        // step that waits for the whole step before it, after its last reader: xx writes a slice the y pass has finished with; exchange 2
+        // backwards receives chunk c while xx(c + 1) still reads xsrc, so it goes to a third slice (E, once z / y are done: slab) or to
+        // ydst (pencil); y^-1 writes E (pencil, 1 x P2) or the slice xx has read (slab, one rank).  tests/test_cpu_spectral_op.py runs the
+        // schedule checker on every case.
+        const int E = (P1 > 1) + (P2 > 1) + 1;
+        const int ysrc = P2 > 1 ? 0 : E, ydst = P2 > 1 ? 1 : 0, xsrc = P1 > 1 ? ydst + 1 : ydst, xd = xsrc == 0 ? 1 : 0;
+        const int isrc = P1 > 1 ? (P2 > 1 ? 1 : E) : xd, idst = P2 > 1 ? E : (P1 > 1 ? 1 : 0), zsrc = P2 > 1 ? (P1 > 1 ? 0 : 1) : idst;
+        pl.spec.steps = {{G_FZ, zf, BUF_IN, E, -1, x1, false, 1, false, DFFT_FORWARD},
+                         {G_FY, FORM_FWD, ysrc, ydst, -1, x2, false, 1, false, DFFT_FORWARD},
+                         {G_XX, FORM_FIXED, xsrc, xd, -1, x2, true, 1, false, DFFT_INVERSE},
+                         {G_IY, FORM_INV, isrc, idst, -1, x1, true, 1, false, DFFT_INVERSE},
+                         {G_IZ, zi, zsrc, BUF_OUT, -1, 0, P2 == 1, 1, false, DFFT_INVERSE}};
+        pl.spec.split = true;
+    }
     // partial transforms: d = 1 stops after the z pass with the natural stage layout [xs][ys][Nzc]; d = 2 after the y pass with
     // [xs][Ny][zs] (z contiguous)
     pl.fwd[0].steps = {{G_PZ1, zf, BUF_IN, BUF_OUT}};

@@ -56,6 +56,8 @@ struct Launch {
     size_t lent = SIZE_MAX, sent = SIZE_MAX;   // byte offsets of the per-point address tables (SIZE_MAX: none)
     size_t in_off = 0;        // byte offset added to the stage's input buffer
     size_t out_off = 0;       // byte offset added to the stage's output buffer
+    size_t mult_off = 0;      // xx launches: element offset of the chunk's first ky row in the multiplier array ...
+    size_t ty_off = 0;        // ... and in the ky table (dfft_spectral_op)
 };
 struct A2A {
     std::vector<size_t> sc, sd, rc, rd;   // bytes, absolute displacements in the stage buffers
@@ -71,6 +73,8 @@ enum GroupId {
                                           // inverse x pass (z passes: fz / iz, forward x pass: fx)
     G_YZ,                                 // Y_Then_ZX: final z pass (x pass = fx, y chunks = fy)
     G_SZ, G_SX, G_SY,                     // single-rank complex plans, pass order z, x, y (build_pipeline_single): natural -> L1 -> L2 -> natural
+    G_XX,                                 // option spectral_op: forward x pass, pointwise multiplier and inverse x pass in one launch per ky chunk
+                                          // (fft_spectral_kernel): the load side of fx restricted to the chunk's ky rows, the store side of ix[c]
     NGROUPS
 };
 struct Group {
@@ -98,6 +102,8 @@ struct Step {
     bool whole = false;    // chunk c waits for the whole step before it (else for chunk c of it only)
     int per_chunk = 1;     // launches per chunk
     bool conj = false;     // launched with conjugation (swap = 1)
+    int tables = 0;        // direction whose exchange tables `xchg` uses: DFFT_FORWARD f1 / f2, DFFT_INVERSE i1 / i2; 0 = the chain's own
+                           // direction (the spectral-operator chain runs forward exchanges before its xx step and inverse ones after)
 };
 struct Chain {
     std::vector<Step> steps;
@@ -107,10 +113,13 @@ struct Chain {
 struct Pipeline {
     int C = 1;
     Group groups[NGROUPS] = {{"fz", 0}, {"fy", 1}, {"fx", 2}, {"ix", 2}, {"iy", 1}, {"iz", 0}, {"pz1", 0}, {"qz1", 0}, {"py2", 1},
-                             {"qy2", 1}, {"zy", 1}, {"ziy", 1}, {"zix", 2}, {"yz", 0}, {"sz", 0}, {"sx", 2}, {"sy", 1}};
+                             {"qy2", 1}, {"zy", 1}, {"ziy", 1}, {"zix", 2}, {"yz", 0}, {"sz", 0}, {"sx", 2}, {"sy", 1}, {"xx", 2}};
     // execution chains: fwd[d - 1] / inv[d - 1] of dfft_exec_dim (d = 3: the whole transform); one_fwd / one_inv the alternatives of a
     // single rank's complex plan (one_rank_alternative): the z, x, y order, or (one_inv alone) the forward launches with conjugation
     Chain fwd[3], inv[3], one_fwd, one_inv;
+    // option spectral_op (dfft_exec_spectral_op): z -> ex1 -> y -> ex2 -> xx -> ex2^-1 -> y^-1 -> ex1^-1 -> z^-1 on work slices alone
+    // (`in` is only read, `out` only written by z^-1); empty without the option
+    Chain spec;
     bool single = false;                       // the z, x, y order is built
     size_t single_work_elems = 0;              // size of the padded L2 buffer
     std::vector<A2A> f1, f2, i2, i1;          // per chunk exchange tables
@@ -149,6 +158,8 @@ struct Options {
     int spectral = 0;        // 1: the spectrum is kept x-contiguous, [yo][zs][Nx] (lines along kx natural), instead of the reference's
                              // [Nx][yo][zs]: the forward x pass stores natural lines and the inverse x pass loads them -- neither
                              // touches the point-major layout whose strided read is the slowest pass of every multi-rank plan
+    int spectral_op = 0;     // 1: the plan also builds the fused forward-multiply-inverse chain (Pipeline::spec, group xx) and one more
+                             // work slice for it; 0: nothing of it exists
     int compute_streams = -1; // 2: the pipeline chunks of a pass alternate over two compute streams, so that the drain of chunk c
                              // overlaps the ramp of chunk c + 1 (a chunk launch of 0.1-0.2 ms pays ~20 us of launch / drain / ramp when
                              // the chunks queue up behind each other on one stream).  -1 = by measurement
@@ -197,7 +208,8 @@ struct dfft_plan {
     std::vector<TimedSpan> spans;
     size_t nspans = 0;
     int last_dir = -1;
-    std::vector<dfft_trace_op> trace_log[2];   // option trace: what the last forward / inverse exec issued
+    std::vector<dfft_trace_op> trace_log[3];   // option trace: what the last forward / inverse / spectral-operator exec issued
+    dfft_spectral_op op{};                     // the multiplier of the spectral-operator exec being enqueued
     // hipGraph replay of single-rank execs (launch-bound small grids): one instantiated graph per (operation, in, out)
     struct GraphEntry { int kind; const void *in; void *out; int uses; hipGraphExec_t exec; };
     std::vector<GraphEntry> graphs;

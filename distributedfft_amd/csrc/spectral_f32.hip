@@ -1,0 +1,35 @@
+// spectral_f32.hip -- fft_spectral_kernel (fft_pass.hip.h), f32: the fused forward-multiply-inverse x pass of dfft_exec_spectral_op for the
+// power-of-two lengths 2 .. 2048, each with the default (variant 0) configuration of its length.  Compiled in two parts (-DDFFT_PART =
+// 0: the array multiplier and the entry points, 1: the table multipliers).
+#include "cfg_f32.hip.h"
+
+namespace dfft {
+#define DFFT_F32_SPECTRAL(X) X(2, 0, F32_2) X(4, 0, F32_4) X(8, 0, F32_8) X(16, 0, F32_16) X(32, 0, F32_32) X(64, 0, F32_64) \
+    X(128, 0, F32_128) X(256, 0, F32_256) X(512, 0, F32_512) X(1024, 0, F32_1024) X(2048, 0, F32_2048)
+int launch_spectral_f32_p0(int N, const PassArgs &A, hipStream_t stream);
+int launch_spectral_f32_p1(int N, const PassArgs &A, hipStream_t stream);
+#if DFFT_PART == 0
+int launch_spectral_f32_p0(int N, const PassArgs &A, hipStream_t stream)
+{
+    switch (N) { DFFT_F32_SPECTRAL(DFFT_CASE_SPECTRAL) }
+    return -1;
+}
+int launch_spectral_f32(int N, const PassArgs &A, hipStream_t stream)
+{
+    return A.mkind == 0 ? launch_spectral_f32_p0(N, A, stream) : launch_spectral_f32_p1(N, A, stream);
+}
+bool spectral_supported_f32(int N)
+{
+    switch (N) { DFFT_F32_SPECTRAL(DFFT_CASE_SPECTRAL_OK) }
+    return false;
+}
+#elif DFFT_PART == 1
+int launch_spectral_f32_p1(int N, const PassArgs &A, hipStream_t stream)
+{
+    switch (N) { DFFT_F32_SPECTRAL(DFFT_CASE_SPECTRAL) }
+    return -1;
+}
+#else
+#error "DFFT_PART must be 0 or 1"
+#endif
+}  // namespace dfft

@@ -56,6 +56,8 @@ enum dfft_kind {
 };
 enum dfft_precision { DFFT_F32 = 0, DFFT_F64 = 1 };   /* template parameter T = float|double */
 enum dfft_direction { DFFT_FORWARD = -1, DFFT_INVERSE = 1 };
+/* third "direction" of the debug interface (dfft_debug_get_chain, dfft_debug_trace_chain): the chain of dfft_exec_spectral_op */
+#define DFFT_SPECTRAL_OP 2
 
 /* struct Configurations, include/params.hpp:83-93.  comm/send method enums are accepted and
  * recorded; the device exchange always runs as one grouped all-to-all per exchange. */
@@ -190,6 +192,12 @@ int dfft_get_pipeline_chunks(const dfft_plan *plan);
  *                      plan.  For callers that go forward -> pointwise work on the spectrum -> inverse (the reference's testcase 4,
  *                      tests/src/pencil/random_dist_3D.cu:748-793, does exactly that) and can index through the strides.
  *                      getOutSize / getOutStart / the exchange tables are unchanged.  Pencil and default slab plans, any rank count.
+ *   "spectral_op"      0 (default) | 1, before dfft_init: the plan also builds what dfft_exec_spectral_op runs -- forward transform,
+ *                      pointwise multiplier, inverse transform as ONE chain whose forward and inverse x passes are a single launch
+ *                      (the spectrum never reaches memory).  It costs one more domain-sized slice of the work area
+ *                      (dfft_work_size_device reports it) and nothing else: with 0 no size, launch or chain of the plan differs.  Pencil
+ *                      and default slab plans, any rank count, both "spectral_layout" settings, C2C and R2C; the x length must be a power
+ *                      of two up to 2048 (dfft_init: ERR_UNSUPPORTED otherwise, and for the Z_Then_YX / Y_Then_ZX sequences).
  *   "graph"            1: a single-rank plan replays the kernel launches of an exec as one hipGraph from the second call
  *                      with the same (operation, in, out) on; 0 (default): plain launches -- measured 6-8 us faster per
  *                      exec on ROCm 7.2 (profiles/r2_graph_latency.txt)
@@ -237,6 +245,27 @@ int dfft_exec_c2c(dfft_plan *plan, void *out, void *in, int direction);
 int dfft_exec_dim(dfft_plan *plan, void *out, void *in, int direction, int d);
 /* non-blocking variants: enqueue only (caller synchronises the stream) */
 int dfft_enqueue_c2c(dfft_plan *plan, void *out, void *in, int direction);
+
+/* new: out = IFFT(m * FFT(in)), unnormalised (times Nx*Ny*Nz; fold 1/(Nx*Ny*Nz) into `scale`), in one call -- the loop of the reference's
+ * testcase 4 (tests/src/pencil/random_dist_3D.cu:685-811: forward, multiply by -|k|^2, inverse).  `in` and `out` are both blocks of the
+ * INPUT layout [xs][ys][Nz] (real for an R2C plan); `in` is only read, out == in is refused (ERR_ARG).  The last forward pass and the first
+ * inverse pass both work on complete x lines of one rank, so they run as one kernel with the multiplier between them: 11 (array) or 10
+ * (tables) trips of a domain-sized buffer through memory instead of the 15 of exec_r2c + a pointwise kernel + exec_c2r.
+ * The multiplier m(kx, ky, kz) over the rank's spectrum block (dfft_get_out_size / dfft_get_out_start):
+ *   kind 0  scale * mult[...]: a complex device array of the plan's precision in the layout of the spectrum block, i.e. indexed through
+ *           dfft_get_out_strides ([Nx][yo][zs], or [yo][zs][Nx] with "spectral_layout" = 1)
+ *   kind 1  scale * (ax[kx] + ay[ky] + az[kz]): three real device tables of the plan's precision with Nx, yo, zs entries, local to the
+ *           block (entry 0 of ay is global ky = out_start[1])
+ *   kind 2  scale / (ax[kx] + ay[ky] + az[kz]), and 0 where the sum is 0 (a Poisson solve next to kind 1's Laplacian)
+ * The plan must have been initialised with option "spectral_op" = 1 (ERR_STATE otherwise).  Blocking, like dfft_exec_r2c; collective on a
+ * multi-rank plan.  No phase timing and no hipGraph replay for this chain. */
+typedef struct dfft_spectral_op {
+    int32_t kind;           /* 0 array, 1 sum of tables, 2 reciprocal of the sum of tables */
+    double scale;
+    const void *mult;       /* kind 0 */
+    const void *ax, *ay, *az;   /* kind 1, 2 */
+} dfft_spectral_op;
+int dfft_exec_spectral_op(dfft_plan *plan, void *out, const void *in, const dfft_spectral_op *op);
 
 /* getInSize/getInStart/getOutSize/getOutStart   include/mpicufft_pencil.hpp:112-122
  * (getOutStart returns start_z of the z split -- the reference indexes start_x there, a bug) */
@@ -324,7 +353,7 @@ typedef struct dfft_pass_desc {
  * addresses.  Any of the arrays may be NULL.  (A caller can pin the same choices on another plan with the "variant_<pass>" /
  * "order_<pass>" options.) */
 int dfft_get_pass_choices(const dfft_plan *plan, int variant[6], int order[6], int addr64[6]);
-/* name: "fz" "fy" "ix" "iy" "iz" "py2" "qy2" "zy" "ziy" (index = chunk, or chunk*P + peer for zy/ziy)
+/* name: "fz" "fy" "ix" "iy" "iz" "py2" "qy2" "xx" "zy" "ziy" (index = chunk, or chunk*P + peer for zy/ziy; "xx": option "spectral_op")
  * and "fx" "zix" "yz" "pz1" "qz1" "sz" "sx" "sy" (index 0; the last three: single-rank complex plans, order z, x, y).  Returns nonzero if the plan has no such launch. */
 int dfft_debug_get_pass(const dfft_plan *plan, const char *name, int index, dfft_pass_desc *desc);
 /* One step of the chain an exec would run now (dfft_debug_get_chain): the launches of a group, chunk by chunk, each chunk followed by
@@ -341,9 +370,11 @@ typedef struct dfft_chain_step {
                              * dfft_get_pipeline_tables reports for the exec's direction */
     int32_t split;          /* the same for every step of a chain: 1 if its chunks may alternate over two compute streams (option
                              * "compute_streams") */
+    int32_t tables;         /* DFFT_FORWARD / DFFT_INVERSE: the direction whose dfft_get_pipeline_tables the step's exchange uses -- the
+                             * chain's own, except in the chain of dfft_exec_spectral_op: forward up to its "xx" step, inverse from it on */
 } dfft_chain_step;
-/* the steps of the chain the next exec in `direction` of `dims` dimensions (1, 2: exec_dim's partial transforms; 3: the whole
- * transform) would run, as options read at exec time choose it; *count receives the number of steps, at most `capacity` are written */
+/* the steps of the chain the next exec in `direction` (DFFT_SPECTRAL_OP with dims = 3: dfft_exec_spectral_op) of `dims` dimensions
+ * (1, 2: exec_dim's partial transforms; 3: the whole transform) would run, as options read at exec time choose it; *count receives the number of steps, at most `capacity` are written */
 int dfft_debug_get_chain(const dfft_plan *plan, int direction, int dims, dfft_chain_step *steps, int capacity, int *count);
 /* One operation of the stream and event schedule of an exec (dfft_debug_trace_chain), in the order the exec issues them.  The executor
  * (run_chain, csrc/dfft.hip) has one loop that decides the schedule; its launches, exchanges, event records and stream waits go through

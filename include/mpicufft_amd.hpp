@@ -218,6 +218,10 @@ public:
     virtual void execR2C(void *out, const void *in) { if (plan_) timed(DFFT_FORWARD, [&] { return dfft_exec_r2c(plan_, out, in); }); }
     virtual void execC2R(void *out, const void *in) { if (plan_) timed(DFFT_INVERSE, [&] { return dfft_exec_c2r(plan_, out, const_cast<void *>(in)); }); }
     void execC2C(void *out, void *in, int direction) { if (plan_) timed(direction, [&] { return dfft_exec_c2c(plan_, out, in, direction); }); }
+    // extension (no counterpart in the reference): out = IFFT(m * FFT(in)), unnormalised, as one chain whose forward and inverse x
+    // passes are a single kernel with the multiplier between them (dfft_exec_spectral_op in dfft_c.h: an array in the spectrum's layout,
+    // or three 1-D tables).  setOption("spectral_op", 1) before initFFT; `in` is only read; no timer sections.
+    void execSpectralOp(void *out, const void *in, const dfft_spectral_op &op) { if (plan_) check(dfft_exec_spectral_op(plan_, out, in, &op)); }
     // extension (no counterpart in the reference): buffers on the physical backing this plan's passes run fastest on, see
     // dfft_tune_placement in dfft_c.h; free them with dfft_free.  Collective on a multi-rank plan.
     void tunePlacement(const void *in, int tries, void **out, void **back = nullptr)

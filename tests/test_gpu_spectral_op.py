@@ -1,0 +1,260 @@
+"""execSpectralOp (option "spectral_op", include/dfft_c.h: dfft_exec_spectral_op): out = IFFT(m * FFT(in)) as one chain whose forward
+and inverse x passes are a single kernel (fft_spectral_kernel) with the multiplier between them -- the loop of the reference's testcase 4
+(tests/src/pencil/random_dist_3D.cu:685-811) in one call.
+
+Reference: numpy in float64, irfftn(rfftn(u) * m) * n resp. ifftn(fftn(u) * m) * n, with u and m rounded to the plan's precision first.
+Metric: the project's per-entry one (tests/parity_metric.py), rms_rel(got, want) <= 2 * forward_bound(prec, n): two transforms, each held
+to the per-entry forward bound; |m| <= 1 so the multiplier adds nothing.  Inputs are zero-mean (uniform - 127.5).  The x lengths run
+through every chain depth and configuration family of the kernel: 16 (one pass), 64 (two), 512 (three), 1024, 2048."""
+import functools
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+import distributedfft_amd as dfft  # noqa: E402
+from oracle import oracle as orc  # noqa: E402
+
+from parity_metric import CENTER, forward_bound, rms, rms_rel, worst_entry  # noqa: E402
+from test_gpu_parity import CDT, NPDT, NPR, RDT, TOL_RT, rel  # noqa: E402
+
+SHAPES = [(16, 8, 16), (64, 24, 20), (512, 8, 16), (1024, 8, 8), (2048, 8, 16)]
+GRIDS = [(1, 1), (2, 1), (1, 2), (2, 2)]
+
+
+def make_plans(shape, P1, P2, prec, c2c, layout, chunks=None):
+    P = P1 * P2
+    world = dfft.Comm.local(P) if P > 1 else None
+    plans = []
+    for r in range(P):
+        pl = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), world, precision=prec, rank=r)
+        if chunks is not None:
+            pl.setPipelineChunks(chunks)
+        pl.setOption("spectral_op", 1)
+        pl.setOption("spectral_layout", layout)
+        pl.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(P1, P2), True, c2c=c2c)
+        plans.append(pl)
+    return plans
+
+
+def in_block(pl, a):
+    (nx, ny, nz), (x0, y0, z0) = pl.getInSize(), pl.getInStart()
+    return np.ascontiguousarray(a[x0:x0 + nx, y0:y0 + ny, z0:z0 + nz])
+
+
+def spectrum_block(pl, a):
+    (_, ny, nz), (_, y0, z0) = pl.getOutSize(), pl.getOutStart()
+    return np.ascontiguousarray(a[:, y0:y0 + ny, z0:z0 + nz])
+
+
+def device_multiplier(pl, prec, m):
+    """the rank's block of the multiplier as a device array in the plan's spectral layout"""
+    esz = 16 if prec == "double" else 8
+    t = torch.zeros(pl.getDomainSize() // esz, dtype=CDT[prec], device="cuda")
+    pl.spectrumView(t).copy_(torch.from_numpy(spectrum_block(pl, m).astype(NPDT[prec])).cuda())
+    return t
+
+
+def device_tables(pl, prec, tables):
+    (_, ny, nz), (_, y0, z0) = pl.getOutSize(), pl.getOutStart()
+    ax, ay, az = tables
+    dev = lambda v: torch.from_numpy(np.ascontiguousarray(v).astype(NPR[prec])).cuda()      # noqa: E731
+    return dev(ax), dev(ay[y0:y0 + ny]), dev(az[z0:z0 + nz])
+
+
+def run_op(plans, prec, c2c, u, m=None, tables=None, reciprocal=False, scale=1.0):
+    """execSpectralOp on every rank (one host thread each); returns the ranks' output blocks.  `in` must come back bit for bit."""
+    P = len(plans)
+    dt = NPDT[prec] if c2c else NPR[prec]
+    ins = [torch.from_numpy(in_block(pl, u).astype(dt)).cuda() for pl in plans]
+    before = [t.cpu().numpy().tobytes() for t in ins]
+    outs = [torch.full_like(t, float("nan")) for t in ins]
+    if m is not None:
+        args = [dict(multiplier=device_multiplier(pl, prec, m), scale=scale) for pl in plans]
+    else:
+        args = [dict(tables=device_tables(pl, prec, tables), reciprocal=reciprocal, scale=scale) for pl in plans]
+    torch.cuda.synchronize()
+    with ThreadPoolExecutor(P) as ex:
+        list(ex.map(lambda r: plans[r].execSpectralOp(outs[r], ins[r], **args[r]), range(P)))
+    torch.cuda.synchronize()
+    for r in range(P):
+        assert ins[r].cpu().numpy().tobytes() == before[r], f"rank {r}: execSpectralOp modified its input"
+    return [t.cpu().numpy() for t in outs]
+
+
+@functools.lru_cache(maxsize=None)
+def reference(shape, prec, c2c):
+    """(u, m, want): zero-mean input and a multiplier with |m| <= 1 -- the transform of a seeded random real-space kernel, so Hermitian-
+    consistent -- both rounded to the plan's precision, and numpy's float64 answer.  Computed once per (shape, precision, kind)."""
+    rng = np.random.default_rng(20261017)
+    n = float(np.prod(shape))
+    kernel = rng.standard_normal(shape)
+    if c2c:
+        u = (rng.uniform(0, 255, shape) - CENTER) + 1j * (rng.uniform(0, 255, shape) - CENTER)
+        u = u.astype(NPDT[prec]).astype(np.complex128)
+        m = np.fft.fftn(kernel)
+        m = (m / np.abs(m).max()).astype(NPDT[prec]).astype(np.complex128)
+        want = np.fft.ifftn(np.fft.fftn(u) * m) * n
+    else:
+        u = (rng.uniform(0, 255, shape) - CENTER).astype(NPR[prec]).astype(np.float64)
+        m = np.fft.rfftn(kernel)
+        m = (m / np.abs(m).max()).astype(NPDT[prec]).astype(np.complex128)
+        want = np.fft.irfftn(np.fft.rfftn(u) * m, s=shape, axes=(0, 1, 2)) * n
+    for a in (u, m, want):
+        a.setflags(write=False)
+    return u, m, want
+
+
+def check(plans, outs, want, prec, what):
+    n = int(np.prod(want.shape))
+    want_rms, bound = rms(want), 2 * forward_bound(prec, n)
+    for r, pl in enumerate(plans):
+        ref = in_block(pl, want)
+        assert not np.isnan(outs[r]).any(), f"{what} rank {r}: part of the output was not written"
+        v = rms_rel(outs[r], ref, want_rms)
+        assert v <= bound, f"{what} rank {r}: per-entry error {v:.3e} > {bound:.1e}; " + worst_entry(outs[r], ref, want_rms)
+
+
+@pytest.mark.parametrize("prec", ["double", "float"])
+@pytest.mark.parametrize("c2c", [True, False], ids=["c2c", "r2c"])
+@pytest.mark.parametrize("P1,P2", GRIDS)
+@pytest.mark.parametrize("shape", SHAPES)
+def test_array_multiplier_against_numpy(shape, P1, P2, c2c, prec):
+    u, m, want = reference(shape, prec, c2c)
+    for layout in (0, 1):
+        plans = make_plans(shape, P1, P2, prec, c2c, layout)
+        check(plans, run_op(plans, prec, c2c, u, m=m), want, prec, f"layout {layout}")
+
+
+@pytest.mark.parametrize("prec", ["double", "float"])
+@pytest.mark.parametrize("layout", [0, 1])
+def test_ragged_tiles(layout, prec):
+    """R2C on (64, 24, 38) over 2 x 3: Nzc = 20 -> 7 + 7 + 6 lines per ky row, no tile is full"""
+    shape = (64, 24, 38)
+    u, m, want = reference(shape, prec, False)
+    plans = make_plans(shape, 2, 3, prec, False, layout)
+    check(plans, run_op(plans, prec, False, u, m=m), want, prec, "2 x 3")
+
+
+@pytest.mark.parametrize("prec", ["double", "float"])
+@pytest.mark.parametrize("chunks", [1, 3])
+def test_pipeline_depths(chunks, prec):
+    shape = (64, 24, 20)
+    for c2c in (True, False):
+        u, m, want = reference(shape, prec, c2c)
+        plans = make_plans(shape, 2, 2, prec, c2c, 0, chunks=chunks)
+        assert plans[0].getPipelineChunks() == chunks and plans[0].debugChain(dfft.SPECTRAL_OP)[2]["launches"] == chunks
+        check(plans, run_op(plans, prec, c2c, u, m=m), want, prec, f"depth {chunks} c2c={c2c}")
+
+
+def wavenumbers(n, half=False):
+    """the reference's derivativeCoefficients (random_dist_3D.cu:98-121): k below n/2, n - k above, 0 at n/2; the Hermitian axis holds
+    k = 0 .. n/2 only"""
+    k = np.arange(n // 2 + 1 if half else n, dtype=np.float64)
+    return np.where(k < n // 2, k, 0.0 if half else np.where(k > n // 2, n - k, 0.0))
+
+
+@pytest.mark.parametrize("layout", [0, 1])
+@pytest.mark.parametrize("shape,P1,P2", [((32, 32, 32), 1, 1), ((32, 32, 32), 2, 4), ((64, 32, 16), 2, 2)])
+def test_testcase4_in_one_call(shape, P1, P2, layout):
+    """the reference's testcase 4 -- u = sin sin sin, spectrum times -(k1^2 + k2^2 + k3^2) / sqrt(n), unnormalised inverse -- as ONE call:
+    tables ax = -kx^2, ay = -ky^2, az = -kz^2, held to the bound of test_testcase4_laplacian_through_the_strides against the same closed
+    form.  sqrt(n) is the reference's own: sqrtf of the int product (oracle.testcase4_root), which is what testcase4_expected divides by."""
+    Nx, Ny, Nz = shape
+    x, y, z = np.meshgrid(np.arange(Nx), np.arange(Ny), np.arange(Nz), indexing="ij")
+    u = np.sin(2 * np.pi * x / Nx) * np.sin(2 * np.pi * y / Ny) * np.sin(2 * np.pi * z / Nz)
+    tables = (-wavenumbers(Nx) ** 2, -wavenumbers(Ny) ** 2, -wavenumbers(Nz, half=True) ** 2)
+    plans = make_plans(shape, P1, P2, "double", False, layout)
+    outs = run_op(plans, "double", False, u, tables=tables, scale=1.0 / orc.testcase4_root(shape))
+    n3 = float(Nx * Ny * Nz)
+    for r, pl in enumerate(plans):
+        assert np.max(np.abs(outs[r] - orc.testcase4_expected(shape, in_block(pl, u)))) < 1e-9 * np.sqrt(n3)
+
+
+def laplacian_tables(shape, c2c):
+    k = lambda n: np.minimum(np.arange(n), n - np.arange(n)).astype(np.float64)      # noqa: E731  (|k|, n/2 at the Nyquist point)
+    Nx, Ny, Nz = shape
+    return -k(Nx) ** 2, -k(Ny) ** 2, -(k(Nz) if c2c else np.arange(Nz // 2 + 1, dtype=np.float64)) ** 2
+
+
+# Shapes: dividing by |k|^2 gives back at low k what the rounding of the Laplacian (eps * its own size, which the highest k set) left
+# there, so the round trip is good to eps * rms(|k|^2), whatever code runs it: 6e-8 * ~100 on the small grids (TOL_RT is 5e-5 at fp32),
+# 1e-16 * ~1e5 on 1024 points at fp64 (TOL_RT 1e-10).  1024 points at fp32 would be 7e-3 by that arithmetic and is not a case.
+POISSON = [((16, 8, 16), 1, 1, "double"), ((16, 8, 16), 1, 1, "float"), ((16, 8, 16), 2, 2, "double"), ((16, 8, 16), 2, 2, "float"),
+           ((32, 8, 8), 2, 1, "double"), ((32, 8, 8), 2, 1, "float"), ((1024, 8, 8), 1, 2, "double")]
+
+
+@pytest.mark.parametrize("c2c", [True, False], ids=["c2c", "r2c"])
+@pytest.mark.parametrize("shape,P1,P2,prec", POISSON)
+def test_laplacian_then_poisson_returns_the_field(shape, P1, P2, c2c, prec):
+    """table form (-|k|^2, normalised), then its reciprocal on the result: the field comes back, without its mean -- the one entry whose
+    table sum is 0 is multiplied by 0, not by 1/0"""
+    u, _, _ = reference(shape, prec, c2c)
+    n = float(np.prod(shape))
+    tables = laplacian_tables(shape, c2c)
+    plans = make_plans(shape, P1, P2, prec, c2c, 0)
+    lap = run_op(plans, prec, c2c, u, tables=tables, scale=1.0 / n)
+    full = np.zeros(shape, dtype=np.complex128 if c2c else np.float64)
+    for r, pl in enumerate(plans):
+        (nx, ny, nz), (x0, y0, z0) = pl.getInSize(), pl.getInStart()
+        full[x0:x0 + nx, y0:y0 + ny, z0:z0 + nz] = lap[r]
+    spec = np.fft.fftn(u) if c2c else np.fft.rfftn(u)
+    kx, ky, kz = np.meshgrid(*tables, indexing="ij")
+    want_lap = np.fft.ifftn(spec * (kx + ky + kz)) if c2c else np.fft.irfftn(spec * (kx + ky + kz), s=shape, axes=(0, 1, 2))
+    assert rel(full, want_lap) < TOL_RT[prec]
+    back = run_op(plans, prec, c2c, full, tables=tables, reciprocal=True, scale=1.0 / n)
+    for r, pl in enumerate(plans):
+        assert rel(back[r], in_block(pl, u - u.mean())) < TOL_RT[prec]
+    # a constant field has nothing but the entry with the zero sum: every output is exactly 0 (with 1/0 there it would be inf or NaN)
+    const = run_op(plans, prec, c2c, np.full(shape, 3.0, dtype=full.dtype), tables=tables, reciprocal=True, scale=1.0 / n)
+    for r in range(len(plans)):
+        assert np.all(const[r] == 0), f"rank {r}: the entry with a zero table sum was not zeroed"
+
+
+@pytest.mark.parametrize("prec", ["double", "float"])
+@pytest.mark.parametrize("shape,P1,P2,layout", [((64, 24, 20), 2, 2, 0), ((64, 24, 20), 2, 2, 1), ((1024, 8, 8), 1, 1, 0), ((2048, 8, 16), 1, 2, 1)])
+def test_agrees_with_the_unfused_path(shape, P1, P2, layout, prec):
+    """same plans, input and multiplier: execR2C -> multiply on spectrumView -> execC2R against the fused call (not bit for bit: the fused
+    x pass runs the default configuration of its length in both directions)"""
+    u, m, want = reference(shape, prec, False)
+    plans = make_plans(shape, P1, P2, prec, False, layout)
+    fused = run_op(plans, prec, False, u, m=m)
+    P, esz = len(plans), 16 if prec == "double" else 8
+    ins = [torch.from_numpy(in_block(pl, u).astype(NPR[prec])).cuda() for pl in plans]
+    specs = [torch.zeros(pl.getDomainSize() // esz, dtype=CDT[prec], device="cuda") for pl in plans]
+    backs = [torch.zeros_like(t) for t in ins]
+    mults = [device_multiplier(pl, prec, m) for pl in plans]
+    torch.cuda.synchronize()
+    with ThreadPoolExecutor(P) as ex:
+        list(ex.map(lambda r: plans[r].execR2C(specs[r], ins[r]), range(P)))
+    for r, pl in enumerate(plans):
+        pl.spectrumView(specs[r]).mul_(pl.spectrumView(mults[r]))
+    torch.cuda.synchronize()
+    with ThreadPoolExecutor(P) as ex:
+        list(ex.map(lambda r: plans[r].execC2R(backs[r], specs[r]), range(P)))
+    torch.cuda.synchronize()
+    n = int(np.prod(shape))
+    want_rms, bound = rms(want), 2 * forward_bound(prec, n)
+    for r in range(P):
+        unfused = backs[r].cpu().numpy().astype(np.float64)
+        v = rms_rel(fused[r], unfused, want_rms)
+        assert v <= bound, f"rank {r}: fused and unfused differ by {v:.3e} > {bound:.1e}; " + worst_entry(fused[r], unfused, want_rms)
+
+
+def test_argument_errors():
+    pl = make_plans((16, 8, 16), 1, 1, "double", False, 0)[0]
+    a = torch.zeros(16 * 8 * 16, dtype=RDT["double"], device="cuda")
+    b = torch.zeros_like(a)
+    m = torch.zeros(pl.getDomainSize() // 16, dtype=CDT["double"], device="cuda")
+    with pytest.raises(dfft.DfftError, match="error 2.*out == in"):      # ERR_ARG: in place is not supported
+        pl.execSpectralOp(a, a, multiplier=m)
+    with pytest.raises(dfft.DfftError):
+        pl.execSpectralOp(b, a)
+    off = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), None, precision="double")
+    off.initFFT(dfft.GlobalSize(16, 8, 16), dfft.Pencil_Partition(1, 1), True)
+    with pytest.raises(dfft.DfftError, match="error 3.*spectral_op"):    # ERR_STATE: the plan was initialised without the option
+        off.execSpectralOp(b, a, multiplier=m)

@@ -1,0 +1,99 @@
+#!/usr/bin/env python
+"""Times the forward -> pointwise multiply -> inverse loop three ways on ONE plan and ONE set of dfft_malloc buffers:
+
+  (a) execR2C + a torch multiply on the spectrum + execC2R        (what a caller writes without execSpectralOp)
+  (b) execSpectralOp with an array multiplier                     (11 trips of a domain-sized buffer through memory instead of 15)
+  (c) execSpectralOp with 1-D tables                              (10 instead of 15)
+
+The paths alternate within one process (a, b, c, a, b, c, ...): warm-ups first, then --reps repetitions each, every path bracketed by
+device events on the stream the plan runs on.  One rank, R2C; shapes N^3 for --sizes, both precisions, both spectral_layout settings.
+Prints one line per configuration and, with --out, appends them to a file.  The spread of (a) over repeated runs of the tool is the
+yardstick for the ratios: run it more than once (--label names the run in the output)."""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import distributedfft_amd as dfft  # noqa: E402
+
+
+def measure(n, prec, layout, reps, warmup):
+    cdt, rdt = (torch.complex128, torch.float64) if prec == "double" else (torch.complex64, torch.float32)
+    esz = 16 if prec == "double" else 8
+    pl = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), None, precision=prec)
+    pl.setOption("spectral_op", 1)
+    pl.setOption("spectral_layout", layout)
+    pl.initFFT(dfft.GlobalSize(n, n, n), dfft.Pencil_Partition(1, 1), True)
+    stream = torch.cuda.current_stream()
+    pl.setStream(stream.cuda_stream)      # the plan's launches and torch's multiply on one stream, between the same two events
+    nreal, dom = n * n * n, pl.getDomainSize()
+    nspec = n * n * (n // 2 + 1)
+    bufs = [dfft.DeviceBuffer.alloc(b) for b in (nreal * esz // 2, nreal * esz // 2, dom, dom)]
+    u, out, spec, mult = bufs[0].tensor(rdt), bufs[1].tensor(rdt), bufs[2].tensor(cdt), bufs[3].tensor(cdt)
+    g = torch.Generator(device="cuda").manual_seed(7)
+    u.copy_(torch.rand(nreal, generator=g, device="cuda", dtype=rdt) * 255 - 127.5)
+    view = torch.view_as_real(mult[:nspec])
+    view.copy_(torch.rand(view.shape, generator=g, device="cuda", dtype=rdt) - 0.5)
+    k = lambda m, half=False: (torch.arange(m // 2 + 1 if half else m, device="cuda", dtype=rdt))      # noqa: E731
+    sq = lambda v, m: -torch.minimum(v, m - v) ** 2      # noqa: E731
+    tables = (sq(k(n), n), sq(k(n), n), sq(k(n, True), n))
+    scale = 1.0 / nreal
+
+    def unfused():
+        pl.execR2C(spec, u)
+        spec[:nspec].mul_(mult[:nspec])      # the two blocks share one layout: a flat product
+        pl.execC2R(out, spec)
+
+    paths = {"a": unfused,
+             "b": lambda: pl.execSpectralOp(out, u, multiplier=mult, scale=scale),
+             "c": lambda: pl.execSpectralOp(out, u, tables=tables, scale=scale)}
+    times = {p: [] for p in paths}
+    for it in range(warmup + reps):
+        for name, fn in paths.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            fn()
+            b.record(stream)
+            b.synchronize()
+            if it >= warmup:
+                times[name].append(a.elapsed_time(b))
+    del u, out, spec, mult
+    for b in bufs:
+        b.free()
+    return {p: (statistics.median(v), min(v), max(v)) for p, v in times.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--sizes", type=int, nargs="+", default=[512, 1024])
+    ap.add_argument("--precisions", nargs="+", default=["double", "float"], choices=["double", "float"])
+    ap.add_argument("--layouts", type=int, nargs="+", default=[0, 1], choices=[0, 1])
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--label", default="")
+    ap.add_argument("--out", default=None, help="append the result lines to this file")
+    args = ap.parse_args()
+    if args.reps < 20:
+        ap.error("--reps must be at least 20")
+    lines = []
+    for n in args.sizes:
+        for prec in args.precisions:
+            for layout in args.layouts:
+                t = measure(n, prec, layout, args.reps, args.warmup)
+                a = t["a"][0]
+                line = (f"{args.label + ' ' if args.label else ''}{n}^3 R2C {prec:<6s} spectral_layout={layout}  reps={args.reps}  ms median (min .. max):  "
+                        + "  ".join(f"({p}) {t[p][0]:8.3f} ({t[p][1]:.3f} .. {t[p][2]:.3f})" for p in "abc")
+                        + f"   b/a = {t['b'][0] / a:.3f} (bytes 11/15 = 0.733)   c/a = {t['c'][0] / a:.3f} (bytes 10/15 = 0.667)")
+                print(line, flush=True)
+                lines.append(line)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
