@@ -42,7 +42,8 @@ class ChainStep(C.Structure):
 
 class SpectralOp(C.Structure):
     """dfft_spectral_op (include/dfft_c.h): the pointwise multiplier of dfft_exec_spectral_op"""
-    _fields_ = [("kind", C.c_int32), ("scale", C.c_double), ("mult", C.c_void_p), ("ax", C.c_void_p), ("ay", C.c_void_p), ("az", C.c_void_p)]
+    _fields_ = [("kind", C.c_int32), ("scale", C.c_double), ("mult", C.c_void_p), ("ax", C.c_void_p), ("ay", C.c_void_p), ("az", C.c_void_p),
+                ("cx", C.c_void_p), ("cy", C.c_void_p), ("cz", C.c_void_p)]
 
 
 class TraceOp(C.Structure):

@@ -375,24 +375,48 @@ class MPIcuFFT:
         f = lib().dfft_exec_c2c if sync else lib().dfft_enqueue_c2c
         check(f(self._h, _ptr(out), _ptr(in_), direction))
 
-    def execSpectralOp(self, out, in_, multiplier=None, tables=None, reciprocal=False, scale=1.0):
+    def execSpectralOp(self, out, in_, multiplier=None, tables=None, reciprocal=False, scale=1.0, factors=None):
         """out = IFFT(m * FFT(in_)), unnormalised, as one chain whose two x passes are a single kernel (dfft_exec_spectral_op; the plan
         needs setOption("spectral_op", 1) before initFFT).  out and in_ are blocks of the input layout; in_ is only read.
         multiplier: complex device array over the spectrum block in the plan's spectral layout (getOutStrides), m = scale * multiplier;
         or tables = (ax, ay, az): real device tables with Nx, yo, zs entries, m = scale * (ax + ay + az) -- with reciprocal=True
-        m = scale / (ax + ay + az), 0 where the sum is 0"""
+        m = scale / (ax + ay + az), 0 where the sum is 0;
+        or factors = (cx, cy, cz): complex device tables with Nx, yo, zs entries, any but not all of them None (a factor of 1),
+        m = scale * cx * cy * cz -- together with tables, m = scale * cx * cy * cz * (ax + ay + az), resp. / (ax + ay + az) with
+        reciprocal=True.  All tables are local to the rank's spectrum block (wavenumbers() gives its kx, ky, kz)."""
         from ._lib import SpectralOp
-        if (multiplier is None) == (tables is None):
-            raise DfftError("execSpectralOp takes either multiplier= or tables=")
-        if multiplier is not None and reciprocal:
+        if multiplier is not None and (tables is not None or factors is not None):
+            raise DfftError("execSpectralOp takes either multiplier= or tables= / factors=")
+        if multiplier is None and tables is None and factors is None:
+            raise DfftError("execSpectralOp takes either multiplier= or tables= / factors=")
+        if reciprocal and tables is None:
             raise DfftError("reciprocal=True needs tables=")
         val = lambda x: None if x is None else _ptr(x).value      # noqa: E731
-        if tables is not None:
+        if factors is not None:
+            cx, cy, cz = factors
+            if cx is None and cy is None and cz is None:
+                raise DfftError("factors= needs at least one table that is not None")
+            ax, ay, az = tables if tables is not None else (None, None, None)
+            kind = 3 if tables is None else 5 if reciprocal else 4
+            op = SpectralOp(kind, float(scale), None, val(ax), val(ay), val(az), val(cx), val(cy), val(cz))
+        elif tables is not None:
             ax, ay, az = tables
             op = SpectralOp(2 if reciprocal else 1, float(scale), None, val(ax), val(ay), val(az))
         else:
             op = SpectralOp(0, float(scale), val(multiplier), None, None, None)
         check(lib().dfft_exec_spectral_op(self._h, _ptr(out), _ptr(in_), C.byref(op)))
+
+    def wavenumbers(self):
+        """(kx, ky, kz): the integer wavenumbers of the rank's spectrum block as host int64 arrays, in the wrapped order
+        0, 1, ..., ceil(n / 2) - 1, -floor(n / 2), ..., -1 of a discrete transform's frequencies -- kx all Nx of them, ky the global ones from getOutStart()[1] on, getOutSize()[1] entries, kz likewise
+        (of an R2C plan: from 0 .. Nz/2).  Entry j of a local table of execSpectralOp belongs to k[j]: the offset and the wrap done once,
+        here.  Host only; works on a plan initialised with allocate=False."""
+        import numpy as np
+        g = self.global_size
+        (_, ny, nz), (_, y0, z0) = self.getOutSize(), self.getOutStart()
+        wrap = lambda n: np.where(np.arange(n) < (n + 1) // 2, np.arange(n), np.arange(n) - n).astype(np.int64)      # noqa: E731
+        kz = wrap(g.Nz) if self.c2c else np.arange(g.Nz // 2 + 1, dtype=np.int64)
+        return wrap(g.Nx), wrap(g.Ny)[y0:y0 + ny], kz[z0:z0 + nz]
 
     def exchange(self, which, direction, sendbuf, recvbuf):
         """only the all-to-all of exchange `which` (1 row group / 2 column group)"""

@@ -2,6 +2,7 @@
 // (mixed_*.hip, rmixed_*.hip) and the generic kernel (bluestein_*.hip) behind plain C symbols that the core library looks up with
 // dlsym.  The library is linked with -Bsymbolic: the dfft:: functions called here are the ones defined in THIS library's objects,
 // not the forwarders of the same name in libdfft_amd.so when that one is in the global scope (the C++ drivers link it directly).
+#include "fft_pass.hip.h"
 #include "dfft_internal.hpp"
 
 namespace dfft {
@@ -16,6 +17,9 @@ bool rmixed_info_f32(int M);
 }  // namespace dfft
 
 extern "C" {
+// what this library was built with: sizeof(PassArgs), sizeof(PassInfo), DFFT_PASS_ABI (fft_pass.hip.h) -- the core library passes both
+// structs by pointer and refuses a library whose numbers differ from its own (any_loader.hip)
+__attribute__((visibility("default"))) void dfft_any_abi(size_t out[3]) { out[0] = sizeof(dfft::PassArgs); out[1] = sizeof(dfft::PassInfo); out[2] = DFFT_PASS_ABI; }
 __attribute__((visibility("default"))) int dfft_any_launch_mixed_f64(int N, int variant, const dfft::PassArgs *A, hipStream_t s) { return dfft::launch_mixed_f64(N, variant, *A, s); }
 __attribute__((visibility("default"))) int dfft_any_launch_mixed_f32(int N, int variant, const dfft::PassArgs *A, hipStream_t s) { return dfft::launch_mixed_f32(N, variant, *A, s); }
 __attribute__((visibility("default"))) int dfft_any_mixed_info_f64(int N, int variant, dfft::PassInfo *pi) { return dfft::mixed_info_f64(N, variant, pi) ? 1 : 0; }

@@ -6,7 +6,7 @@
 // of template instantiations that no BASELINE configuration touches (profiles/r6_cold_build_per_object.txt); they live in
 // libdfft_amd_any.so next to this library (any_exports.hip), which is opened at the first plan that needs one of them.  The
 // functions below are the entry points the rest of the core calls (kernels_*.hip, real_*.hip, dfft.hip: launch_generic); they forward
-// through the C symbols of the second library.  There is no fallback: when it is missing, dfft_init of such a plan fails and says
+// through the C symbols of the second library, after dfft_any_abi has shown that it was built with this library's PassArgs and PassInfo.  There is no fallback: when it is missing, dfft_init of such a plan fails and says
 // which file to build.
 #include <dlfcn.h>
 #include <stdlib.h>
@@ -14,6 +14,7 @@
 #include <mutex>
 #include <string>
 
+#include "fft_pass.hip.h"
 #include "dfft_internal.hpp"
 
 namespace dfft {
@@ -60,6 +61,27 @@ void load_once()
     lib.rmixed_info[0] = (info1_fn)sym("dfft_any_rmixed_info_f64");       lib.rmixed_info[1] = (info1_fn)sym("dfft_any_rmixed_info_f32");
     lib.launch_bluestein[0] = (launch2_fn)sym("dfft_any_launch_bluestein_f64");
     lib.launch_bluestein[1] = (launch2_fn)sym("dfft_any_launch_bluestein_f32");
+    // PassArgs and PassInfo cross the seam by pointer: a library built from another version of either struct is refused
+    if (ok) {
+        using abi_fn = void (*)(size_t[3]);
+        const std::string rebuild = " -- rebuild it with `make -C distributedfft_amd/csrc any`";
+        abi_fn abi = (abi_fn)dlsym(h, "dfft_any_abi");
+        if (!abi) {
+            ok = false;
+            lib.why = path + " lacks the symbol dfft_any_abi (a build from before the check of the kernel argument structs)" + rebuild;
+        } else {
+            size_t theirs[3] = {0, 0, 0};
+            const size_t mine[3] = {sizeof(PassArgs), sizeof(PassInfo), (size_t)DFFT_PASS_ABI};
+            abi(theirs);
+            if (theirs[0] != mine[0] || theirs[1] != mine[1] || theirs[2] != mine[2]) {
+                auto list = [](const size_t v[3]) {
+                    return "sizeof(PassArgs) " + std::to_string(v[0]) + ", sizeof(PassInfo) " + std::to_string(v[1]) + ", DFFT_PASS_ABI " + std::to_string(v[2]);
+                };
+                ok = false;
+                lib.why = path + " was built for another version of the kernel argument structs (" + list(theirs) + "; this library: " + list(mine) + ")" + rebuild;
+            }
+        }
+    }
     if (ok) lib.handle = h; else dlclose(h);
 }
 AnyLib *any()

@@ -394,7 +394,10 @@ static int launch_spectral(dfft_plan *p, const Launch &L, const char *in, char *
     fill_tables(p, L, A);
     A.mkind = op.kind; A.mscale = op.scale;
     if (op.kind == 0) A.mult = static_cast<const char *>(op.mult) + L.mult_off * p->esz;
-    else { A.mtx = op.ax; A.mty = static_cast<const char *>(op.ay) + L.ty_off * real; A.mtz = op.az; }
+    else if (op.kind != 3) { A.mtx = op.ax; A.mty = static_cast<const char *>(op.ay) + L.ty_off * real; A.mtz = op.az; }
+    if (op.kind >= 3) {      // the factor tables; cy starts at the chunk's first ky row like ay, in complex elements
+        A.mcx = op.cx; A.mcy = op.cy ? static_cast<const char *>(op.cy) + L.ty_off * p->esz : nullptr; A.mcz = op.cz;
+    }
     const int r = p->prec == DFFT_F64 ? launch_spectral_f64((int)p->Nx, A, stream) : launch_spectral_f32((int)p->Nx, A, stream);
     if (r == -1) return fail(ERR_UNSUPPORTED, "spectral_op: unsupported x length " + std::to_string(p->Nx));
     if (r != 0) return fail(r, std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)r));
@@ -1363,8 +1366,14 @@ int dfft_exec_spectral_op(dfft_plan *p, void *out, const void *in, const dfft_sp
     TRY(check_ready(p));
     if (!out || !in || !op) return fail(ERR_ARG, "null buffer or operator");
     if (out == in) return fail(ERR_ARG, "spectral_op: out == in is not supported");
-    if (op->kind < 0 || op->kind > 2) return fail(ERR_ARG, "spectral_op: kind must be 0 (array), 1 (sum of tables) or 2 (reciprocal of the sum)");
-    if (op->kind == 0 ? !op->mult : (!op->ax || !op->ay || !op->az)) return fail(ERR_ARG, "spectral_op: null multiplier");
+    if (op->kind < 0 || op->kind > 5)
+        return fail(ERR_ARG, "spectral_op: kind must be 0 (array), 1 (sum of tables), 2 (reciprocal of the sum), 3 (product of factor tables), "
+                             "4 (product times the sum) or 5 (product over the sum)");
+    // the fields a kind does not use are never read: cx, cy, cz were appended, a caller of kinds 0 .. 2 may hold the six-field struct
+    const bool sums = op->kind == 1 || op->kind == 2 || op->kind == 4 || op->kind == 5, factors = op->kind >= 3;
+    if (op->kind == 0 && !op->mult) return fail(ERR_ARG, "spectral_op: null multiplier");
+    if (sums && (!op->ax || !op->ay || !op->az)) return fail(ERR_ARG, "spectral_op: null multiplier (kinds 1, 2, 4 and 5 need all of ax, ay, az)");
+    if (factors && !op->cx && !op->cy && !op->cz) return fail(ERR_ARG, "spectral_op: null multiplier (kinds 3, 4 and 5 need at least one of cx, cy, cz)");
     if (op->kind == 0) {
         // one tile per workgroup: the kernel adds 32-bit lane offsets (t*MK + l*ME elements) to a scalar base per point
         PassInfo pi;
@@ -1373,7 +1382,11 @@ int dfft_exec_spectral_op(dfft_plan *p, void *out, const void *in, const dfft_sp
             ((uint64_t)(pi.N / pi.E) * L->args.MK + (uint64_t)pi.TL * L->args.ME) * p->esz >= (1ull << 32))
             return fail(ERR_UNSUPPORTED, "spectral_op: the multiplier block is too large for the kernel's 32-bit lane offsets");
     }
-    p->op = *op;
+    p->op = dfft_spectral_op{};
+    p->op.kind = op->kind; p->op.scale = op->scale;
+    if (op->kind == 0) p->op.mult = op->mult;
+    if (sums) { p->op.ax = op->ax; p->op.ay = op->ay; p->op.az = op->az; }
+    if (factors) { p->op.cx = op->cx; p->op.cy = op->cy; p->op.cz = op->cz; }
     TRY(run_chain(p, DFFT_SPECTRAL_OP, 3, out, in));
     HIP_TRY(hipStreamSynchronize(p->stream));
     return 0;

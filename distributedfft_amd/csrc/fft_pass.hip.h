@@ -125,12 +125,20 @@ struct PassArgs {
     //   mkind 0: mscale * mult[k*MK + a*MA + e*ME]                 (complex array in the layout of the plan's spectrum block)
     //   mkind 1: mscale * (mtx[k] + mty[a] + mtz[e])               (three real tables)
     //   mkind 2: mscale / (mtx[k] + mty[a] + mtz[e]), 0 where the sum is 0
+    //   mkind 3: mscale * P,  P = mcx[k] * mcy[a] * mcz[e]         (three complex tables; a null table is a factor of 1)
+    //   mkind 4: mscale * P * (mtx[k] + mty[a] + mtz[e])
+    //   mkind 5: mscale * P / (mtx[k] + mty[a] + mtz[e]), 0 where the sum is 0
     int32_t mkind;
     double mscale;
     const void *mult;
     uint64_t MK, MA, ME;
     const void *mtx, *mty, *mtz;
+    const void *mcx, *mcy, *mcz;
 };
+// PassArgs and PassInfo (dfft_internal.hpp) cross the seam between libdfft_amd.so and libdfft_amd_any.so by pointer (any_loader.hip ->
+// any_exports.hip).  Bump this by hand whenever either struct changes: the loader refuses a library built with another value, or with
+// other sizes of the two structs.
+#define DFFT_PASS_ABI 2
 
 // ------------------------------------------------------------------------------------------
 // complex number = native 2-vector.  For fp32 that is the point: a <2 x float> lives in an aligned register pair and its
@@ -1132,9 +1140,29 @@ template <typename Cfg> constexpr int spectral_waves()
     return w < 1 ? 1 : w > 4 ? 4 : w;
 }
 
-// TABLES: 0 = the multiplier is a complex array (PassArgs::mkind 0), 1 = it is built from three real tables (mkind 1, 2).  Two
-// instantiations, not a branch: with both forms in one kernel the transformed registers flow through either and the 1024-point fp64
-// configuration takes 152 VGPRs instead of 128, the 2048-point one spills
+// The per-point product of the factor-table forms (mkind 3, 4, 5), shared by the kernel and by its host emulation
+// (tests/cpp/spectral_factor_check.hip): v = the point after the first chain, cx = mcx[k] (1 for a null table), line = mscale * mcy[a] * mcz[e],
+// sum = (mtx[k] + mty[a]) + mtz[e] (read for mkind 4 and 5 only).  Returns conj(v * f), f = cx * line * g, g = 1 | sum | 1 / sum (0 at a zero
+// sum): the point the second chain starts from.
+template <typename C> __host__ __device__ __forceinline__ C spectral_factor_point(C v, C cx, C line, int mkind, scalar_t<C> sum)
+{
+    using R = scalar_t<C>;
+    C f = cmul2(cx, line, ci(line));
+    if (mkind == 4) f *= sum;
+    else if (mkind == 5) f *= sum != (R)0 ? (R)1 / sum : (R)0;
+    const C y = cmul2(v, f, ci(f));
+    return cmake<C>(y.x, -y.y);
+}
+// the per-line factor of those forms: mscale * cy * cz
+template <typename C> __host__ __device__ __forceinline__ C spectral_factor_line(scalar_t<C> scale, C cy, C cz)
+{
+    return cmul2(cy, cz, ci(cz)) * scale;
+}
+
+// TABLES: 0 = the multiplier is a complex array (PassArgs::mkind 0), 1 = it is built from three real tables (mkind 1, 2), 2 = from three
+// complex tables, with or without the real ones (mkind 3, 4, 5).  Separate instantiations, not a branch: with the array and the table form
+// in one kernel the transformed registers flow through either and the 1024-point fp64 configuration takes 152 VGPRs instead of 128, the
+// 2048-point one spills.  (mkind is uniform over the launch: the branches on it inside TABLES == 2 are scalar.)
 template <typename Cfg, int TABLES>
 __global__ __launch_bounds__(Cfg::THREADS, spectral_waves<Cfg>()) void fft_spectral_kernel(const PassArgs A)
 {
@@ -1196,6 +1224,31 @@ __global__ __launch_bounds__(Cfg::THREADS, spectral_waves<Cfg>()) void fft_spect
                 constexpr int j = decltype(jj)::value, c = q * CH + j, s = spectral_sigma<Cfg>(c);
                 const C y = cmul2(v[c], m[j], ci(m[j])) * scale;
                 w[s].x = y.x; w[s].y = -y.y;
+                settle(w[s]);
+            });
+        });
+    } else if constexpr (TABLES == 2) {
+        // a null table is a factor of 1; a lane without a line gets a line factor of 0 (its data are zeros)
+        const bool sums = A.mkind != 3;
+        const C one = cmake<C>((R)1, (R)0), zero = cmake<C>((R)0, (R)0);
+        const C *cxp = A.mcx ? reinterpret_cast<const C *>(A.mcx) + t2 : nullptr;
+        const C cy = !P.ok ? zero : A.mcy ? reinterpret_cast<const C *>(A.mcy)[P.a] : one;
+        const C cz = !P.ok ? zero : A.mcz ? reinterpret_cast<const C *>(A.mcz)[P.e] : one;
+        const C line = spectral_factor_line<C>(scale, cy, cz);
+        const R *tx = sums ? reinterpret_cast<const R *>(A.mtx) + t2 : nullptr;
+        const R sy = sums && P.ok ? reinterpret_cast<const R *>(A.mty)[P.a] : (R)0, sz = sums && P.ok ? reinterpret_cast<const R *>(A.mtz)[P.e] : (R)0;
+        static_for<0, E / CH>([&](auto qq) {
+            constexpr int q = decltype(qq)::value;
+            C m[CH];
+            R ms[CH];
+            static_for<0, CH>([&](auto jj) {
+                constexpr int j = decltype(jj)::value, s = spectral_sigma<Cfg>(q * CH + j);
+                m[j] = cxp ? cxp[NT * s] : one;
+                ms[j] = sums ? tx[NT * s] : (R)0;
+            });
+            static_for<0, CH>([&](auto jj) {
+                constexpr int j = decltype(jj)::value, c = q * CH + j, s = spectral_sigma<Cfg>(c);
+                w[s] = spectral_factor_point<C>(v[c], m[j], line, A.mkind, (ms[j] + sy) + sz);
                 settle(w[s]);
             });
         });

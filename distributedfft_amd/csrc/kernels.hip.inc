@@ -39,7 +39,7 @@ template <typename Cfg> static int launch_cfg(const PassArgs &A, hipStream_t str
 
 // fft_spectral_kernel (forward transform, pointwise multiplier, inverse transform of complete x lines in one launch): whole tiles,
 // one workgroup per G tiles, the dynamic-LDS attribute as for launch_cfg.  TABLES = the part of spectral_<p>.hip (-DDFFT_PART):
-// 0 array multiplier, 1 table multiplier
+// 0 array multiplier, 1 real table multipliers, 2 complex factor tables
 template <typename Cfg, int TABLES> static int launch_spectral_cfg(const PassArgs &A, hipStream_t stream)
 {
     static bool attr_set = false;

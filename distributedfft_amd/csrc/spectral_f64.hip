@@ -1,6 +1,6 @@
 // spectral_f64.hip -- fft_spectral_kernel (fft_pass.hip.h), f64: the fused forward-multiply-inverse x pass of dfft_exec_spectral_op for the
-// power-of-two lengths 2 .. 2048, each with the default (variant 0) configuration of its length.  Compiled in two parts (-DDFFT_PART =
-// 0: the array multiplier and the entry points, 1: the table multipliers).
+// power-of-two lengths 2 .. 2048, each with the default (variant 0) configuration of its length.  Compiled in three parts (-DDFFT_PART =
+// 0: the array multiplier and the entry points, 1: the real table multipliers, 2: the complex factor tables, mkind 3 .. 5).
 #include "cfg_f64.hip.h"
 
 namespace dfft {
@@ -8,6 +8,7 @@ namespace dfft {
     X(128, 0, F64_128) X(256, 0, F64_256) X(512, 0, F64_512) X(1024, 0, F64_1024) X(2048, 0, F64_2048)
 int launch_spectral_f64_p0(int N, const PassArgs &A, hipStream_t stream);
 int launch_spectral_f64_p1(int N, const PassArgs &A, hipStream_t stream);
+int launch_spectral_f64_p2(int N, const PassArgs &A, hipStream_t stream);
 #if DFFT_PART == 0
 int launch_spectral_f64_p0(int N, const PassArgs &A, hipStream_t stream)
 {
@@ -16,7 +17,7 @@ int launch_spectral_f64_p0(int N, const PassArgs &A, hipStream_t stream)
 }
 int launch_spectral_f64(int N, const PassArgs &A, hipStream_t stream)
 {
-    return A.mkind == 0 ? launch_spectral_f64_p0(N, A, stream) : launch_spectral_f64_p1(N, A, stream);
+    return A.mkind == 0 ? launch_spectral_f64_p0(N, A, stream) : A.mkind <= 2 ? launch_spectral_f64_p1(N, A, stream) : launch_spectral_f64_p2(N, A, stream);
 }
 bool spectral_supported_f64(int N)
 {
@@ -29,7 +30,13 @@ int launch_spectral_f64_p1(int N, const PassArgs &A, hipStream_t stream)
     switch (N) { DFFT_F64_SPECTRAL(DFFT_CASE_SPECTRAL) }
     return -1;
 }
+#elif DFFT_PART == 2
+int launch_spectral_f64_p2(int N, const PassArgs &A, hipStream_t stream)
+{
+    switch (N) { DFFT_F64_SPECTRAL(DFFT_CASE_SPECTRAL) }
+    return -1;
+}
 #else
-#error "DFFT_PART must be 0 or 1"
+#error "DFFT_PART must be 0, 1 or 2"
 #endif
 }  // namespace dfft

@@ -250,20 +250,30 @@ int dfft_enqueue_c2c(dfft_plan *plan, void *out, void *in, int direction);
  * testcase 4 (tests/src/pencil/random_dist_3D.cu:685-811: forward, multiply by -|k|^2, inverse).  `in` and `out` are both blocks of the
  * INPUT layout [xs][ys][Nz] (real for an R2C plan); `in` is only read, out == in is refused (ERR_ARG).  The last forward pass and the first
  * inverse pass both work on complete x lines of one rank, so they run as one kernel with the multiplier between them: 11 (array) or 10
- * (tables) trips of a domain-sized buffer through memory instead of the 15 of exec_r2c + a pointwise kernel + exec_c2r.
+ * (real and complex tables) trips of a domain-sized buffer through memory instead of the 15 of exec_r2c + a pointwise kernel + exec_c2r.
  * The multiplier m(kx, ky, kz) over the rank's spectrum block (dfft_get_out_size / dfft_get_out_start):
  *   kind 0  scale * mult[...]: a complex device array of the plan's precision in the layout of the spectrum block, i.e. indexed through
  *           dfft_get_out_strides ([Nx][yo][zs], or [yo][zs][Nx] with "spectral_layout" = 1)
  *   kind 1  scale * (ax[kx] + ay[ky] + az[kz]): three real device tables of the plan's precision with Nx, yo, zs entries, local to the
  *           block (entry 0 of ay is global ky = out_start[1])
  *   kind 2  scale / (ax[kx] + ay[ky] + az[kz]), and 0 where the sum is 0 (a Poisson solve next to kind 1's Laplacian)
+ *   kind 3  scale * P, P = cx[kx] * cy[ky] * cz[kz]: three COMPLEX device tables of the plan's precision with Nx, yo, zs entries, local to
+ *           the block exactly as ax, ay, az are (entry 0 of cy is global ky = out_start[1]).  A NULL table is a factor of 1; at least one of
+ *           the three must be non-NULL (ERR_ARG).  A derivative i*kx, a Gaussian filter, a translation exp(i k.d): every separable multiplier
+ *           at the traffic of the table forms (10 trips) and Nx + yo + zs entries of memory
+ *   kind 4  scale * P * (ax[kx] + ay[ky] + az[kz])                   (all of ax, ay, az, like kinds 1 and 2)
+ *   kind 5  scale * P / (ax[kx] + ay[ky] + az[kz]), and 0 where the sum is 0 (one component of the gradient of a Poisson solution:
+ *           cx = i*kx, the sums -|k|^2)
+ * cx, cy, cz were appended to the struct: kinds 0 .. 2 never read them, so a caller compiled against the six-field struct stays correct.
  * The plan must have been initialised with option "spectral_op" = 1 (ERR_STATE otherwise).  Blocking, like dfft_exec_r2c; collective on a
  * multi-rank plan.  No phase timing and no hipGraph replay for this chain. */
 typedef struct dfft_spectral_op {
-    int32_t kind;           /* 0 array, 1 sum of tables, 2 reciprocal of the sum of tables */
+    int32_t kind;           /* 0 array, 1 sum of tables, 2 reciprocal of the sum of tables, 3 product of factor tables, 4 product * sum,
+                             * 5 product / sum */
     double scale;
     const void *mult;       /* kind 0 */
-    const void *ax, *ay, *az;   /* kind 1, 2 */
+    const void *ax, *ay, *az;   /* kind 1, 2, 4, 5 */
+    const void *cx, *cy, *cz;   /* kind 3, 4, 5 (read for no other kind) */
 } dfft_spectral_op;
 int dfft_exec_spectral_op(dfft_plan *plan, void *out, const void *in, const dfft_spectral_op *op);
 

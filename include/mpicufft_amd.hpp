@@ -220,7 +220,7 @@ public:
     void execC2C(void *out, void *in, int direction) { if (plan_) timed(direction, [&] { return dfft_exec_c2c(plan_, out, in, direction); }); }
     // extension (no counterpart in the reference): out = IFFT(m * FFT(in)), unnormalised, as one chain whose forward and inverse x
     // passes are a single kernel with the multiplier between them (dfft_exec_spectral_op in dfft_c.h: an array in the spectrum's layout,
-    // or three 1-D tables).  setOption("spectral_op", 1) before initFFT; `in` is only read; no timer sections.
+    // three real 1-D tables (their sum or its reciprocal), or three complex 1-D factor tables cx, cy, cz, alone or times / over that sum).  setOption("spectral_op", 1) before initFFT; `in` is only read; no timer sections.
     void execSpectralOp(void *out, const void *in, const dfft_spectral_op &op) { if (plan_) check(dfft_exec_spectral_op(plan_, out, in, &op)); }
     // extension (no counterpart in the reference): buffers on the physical backing this plan's passes run fastest on, see
     // dfft_tune_placement in dfft_c.h; free them with dfft_free.  Collective on a multi-rank plan.

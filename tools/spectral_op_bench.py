@@ -1,11 +1,12 @@
 #!/usr/bin/env python
-"""Times the forward -> pointwise multiply -> inverse loop three ways on ONE plan and ONE set of dfft_malloc buffers:
+"""Times the forward -> pointwise multiply -> inverse loop four ways on ONE plan and ONE set of dfft_malloc buffers:
 
   (a) execR2C + a torch multiply on the spectrum + execC2R        (what a caller writes without execSpectralOp)
   (b) execSpectralOp with an array multiplier                     (11 trips of a domain-sized buffer through memory instead of 15)
   (c) execSpectralOp with 1-D tables                              (10 instead of 15)
+  (d) execSpectralOp with complex 1-D factor tables               (10 instead of 15; i * kx times a Gaussian in ky and kz)
 
-The paths alternate within one process (a, b, c, a, b, c, ...): warm-ups first, then --reps repetitions each, every path bracketed by
+The paths alternate within one process (a, b, c, d, a, b, c, d, ...): warm-ups first, then --reps repetitions each, every path bracketed by
 device events on the stream the plan runs on.  One rank, R2C; shapes N^3 for --sizes, both precisions, both spectral_layout settings.
 Prints one line per configuration and, with --out, appends them to a file.  The spread of (a) over repeated runs of the tool is the
 yardstick for the ratios: run it more than once (--label names the run in the output)."""
@@ -41,6 +42,9 @@ def measure(n, prec, layout, reps, warmup):
     k = lambda m, half=False: (torch.arange(m // 2 + 1 if half else m, device="cuda", dtype=rdt))      # noqa: E731
     sq = lambda v, m: -torch.minimum(v, m - v) ** 2      # noqa: E731
     tables = (sq(k(n), n), sq(k(n), n), sq(k(n, True), n))
+    wrapped = lambda m: torch.where(k(m) < (m + 1) // 2, k(m), k(m) - m)      # noqa: E731
+    gauss = lambda v: torch.exp(-0.5 * (4.0 / n) ** 2 * v ** 2).to(cdt)      # noqa: E731
+    factors = ((1j * wrapped(n)).to(cdt), gauss(wrapped(n)), gauss(k(n, True)))
     scale = 1.0 / nreal
 
     def unfused():
@@ -50,7 +54,8 @@ def measure(n, prec, layout, reps, warmup):
 
     paths = {"a": unfused,
              "b": lambda: pl.execSpectralOp(out, u, multiplier=mult, scale=scale),
-             "c": lambda: pl.execSpectralOp(out, u, tables=tables, scale=scale)}
+             "c": lambda: pl.execSpectralOp(out, u, tables=tables, scale=scale),
+             "d": lambda: pl.execSpectralOp(out, u, factors=factors, scale=scale)}
     times = {p: [] for p in paths}
     for it in range(warmup + reps):
         for name, fn in paths.items():
@@ -86,8 +91,8 @@ def main():
                 t = measure(n, prec, layout, args.reps, args.warmup)
                 a = t["a"][0]
                 line = (f"{args.label + ' ' if args.label else ''}{n}^3 R2C {prec:<6s} spectral_layout={layout}  reps={args.reps}  ms median (min .. max):  "
-                        + "  ".join(f"({p}) {t[p][0]:8.3f} ({t[p][1]:.3f} .. {t[p][2]:.3f})" for p in "abc")
-                        + f"   b/a = {t['b'][0] / a:.3f} (bytes 11/15 = 0.733)   c/a = {t['c'][0] / a:.3f} (bytes 10/15 = 0.667)")
+                        + "  ".join(f"({p}) {t[p][0]:8.3f} ({t[p][1]:.3f} .. {t[p][2]:.3f})" for p in "abcd")
+                        + f"   b/a = {t['b'][0] / a:.3f} (bytes 11/15 = 0.733)   c/a = {t['c'][0] / a:.3f} (bytes 10/15 = 0.667)   d/a = {t['d'][0] / a:.3f} (bytes 10/15 = 0.667)")
                 print(line, flush=True)
                 lines.append(line)
     if args.out:
