@@ -377,7 +377,8 @@ class MPIcuFFT:
 
     def execSpectralOp(self, out, in_, multiplier=None, tables=None, reciprocal=False, scale=1.0, factors=None):
         """out = IFFT(m * FFT(in_)), unnormalised, as one chain whose two x passes are a single kernel (dfft_exec_spectral_op; the plan
-        needs setOption("spectral_op", 1) before initFFT).  out and in_ are blocks of the input layout; in_ is only read.
+        needs setOption("spectral_op", 1) before initFFT, or 2 where the x length is a mixed-radix one such as 768 or 1000:
+        spectral_op_supported()).  out and in_ are blocks of the input layout; in_ is only read.
         multiplier: complex device array over the spectrum block in the plan's spectral layout (getOutStrides), m = scale * multiplier;
         or tables = (ax, ay, az): real device tables with Nx, yo, zs entries, m = scale * (ax + ay + az) -- with reciprocal=True
         m = scale / (ax + ay + az), 0 where the sum is 0;
@@ -602,6 +603,13 @@ def axis_plan_info(N, precision="double", two_level=0):
     # long_bluestein: Bluestein's algorithm on M padded points, whose M-point transforms run in the two levels listed
     levels = [(info[2], info[3], bool(info[4])), (info[5], info[6], bool(info[7]))] if info[0] >= 2 else []
     return {"kind": kind, "M": info[1], "levels": levels}
+
+
+def spectral_op_supported(n, precision="double", value=2):
+    """whether initFFT accepts an x length of n points under setOption("spectral_op", value) with default options (value 1: powers of two
+    from 2 to 2048; value 2: also the mixed-radix lengths with a fused kernel).  Host only."""
+    prec = {"double": 1, "float": 0}[precision]
+    return bool(lib().dfft_spectral_op_supported(prec, int(n), int(value)))
 
 
 def kernel_info(N, precision="double"):

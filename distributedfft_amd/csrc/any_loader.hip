@@ -2,7 +2,7 @@
 //
 // libdfft_amd.so holds the kernels of the power-of-two lengths 2 .. 8192 (complex axis passes and the packed real z passes): every
 // BASELINE configuration, ~13 core-minutes to compile.  The kernels of every OTHER length -- the 49 mixed-radix lengths 2^a 3^b 5^c 7^d
-// <= 2048, their packed real forms, and the generic kernel (Bluestein passes, two-level lines, long Bluestein) -- are ~45 core-minutes
+// <= 2048, their packed real forms and fused spectral-operator passes, and the generic kernel (Bluestein passes, two-level lines, long Bluestein) -- are ~45 core-minutes
 // of template instantiations that no BASELINE configuration touches (profiles/r6_cold_build_per_object.txt); they live in
 // libdfft_amd_any.so next to this library (any_exports.hip), which is opened at the first plan that needs one of them.  The
 // functions below are the entry points the rest of the core calls (kernels_*.hip, real_*.hip, dfft.hip: launch_generic); they forward
@@ -27,10 +27,13 @@ using info1_fn = int (*)(int);
 struct AnyLib {
     void *handle = nullptr;
     std::string why;                       // why it is not available
+    std::string spectral_why;              // why the fused spectral-operator passes are not (a library from before they existed)
     launch3_fn launch_mixed[2] = {nullptr, nullptr}, launch_rmixed[2] = {nullptr, nullptr};      // [0] f64, [1] f32
     info3_fn mixed_info[2] = {nullptr, nullptr};
     info1_fn rmixed_info[2] = {nullptr, nullptr};
     launch2_fn launch_bluestein[2] = {nullptr, nullptr};
+    launch2_fn launch_spectral_mixed[2] = {nullptr, nullptr};
+    info1_fn spectral_mixed_supported[2] = {nullptr, nullptr};
 };
 AnyLib g_any;
 std::once_flag g_any_once;
@@ -82,6 +85,20 @@ void load_once()
             }
         }
     }
+    // the fused spectral-operator passes of the mixed-radix lengths came later than the rest: a library without them still serves every
+    // other plan, and dfft_init of a plan that needs them (option spectral_op = 2) says what is missing
+    if (ok) {
+        const char *names[4] = {"dfft_any_launch_spectral_mixed_f64", "dfft_any_launch_spectral_mixed_f32",
+                                "dfft_any_spectral_mixed_supported_f64", "dfft_any_spectral_mixed_supported_f32"};
+        void *s[4];
+        for (int i = 0; i < 4; i++)
+            if (!(s[i] = dlsym(h, names[i])) && lib.spectral_why.empty())
+                lib.spectral_why = path + " lacks the symbol " + names[i] + " -- rebuild it with `make -C distributedfft_amd/csrc any`";
+        if (lib.spectral_why.empty()) {
+            lib.launch_spectral_mixed[0] = (launch2_fn)s[0]; lib.launch_spectral_mixed[1] = (launch2_fn)s[1];
+            lib.spectral_mixed_supported[0] = (info1_fn)s[2]; lib.spectral_mixed_supported[1] = (info1_fn)s[3];
+        }
+    }
     if (ok) lib.handle = h; else dlclose(h);
 }
 AnyLib *any()
@@ -99,6 +116,15 @@ bool any_available(std::string *why)
     return false;
 }
 
+// are the fused spectral-operator passes of the mixed-radix lengths there?  (*why: the reason when they are not)
+bool any_spectral_mixed_available(std::string *why)
+{
+    AnyLib *l = any();
+    if (l && l->spectral_why.empty()) return true;
+    if (why) *why = l ? l->spectral_why : g_any.why;
+    return false;
+}
+
 // "no kernel for this length" (-1 / false) when the library is missing, exactly like a length without a configuration: the plan
 // then looks for another form of the axis, ends at the generic kernel, and dfft_init reports why that is not available either
 int launch_mixed_f64(int N, int variant, const PassArgs &A, hipStream_t s) { AnyLib *l = any(); return l ? l->launch_mixed[0](N, variant, &A, s) : -1; }
@@ -111,4 +137,8 @@ bool rmixed_info_f64(int M) { AnyLib *l = any(); return l && l->rmixed_info[0](M
 bool rmixed_info_f32(int M) { AnyLib *l = any(); return l && l->rmixed_info[1](M) != 0; }
 int launch_bluestein_f64(int M, const PassArgs &A, hipStream_t s) { AnyLib *l = any(); return l ? l->launch_bluestein[0](M, &A, s) : -1; }
 int launch_bluestein_f32(int M, const PassArgs &A, hipStream_t s) { AnyLib *l = any(); return l ? l->launch_bluestein[1](M, &A, s) : -1; }
+int launch_spectral_mixed_f64(int N, const PassArgs &A, hipStream_t s) { AnyLib *l = any(); return l && l->launch_spectral_mixed[0] ? l->launch_spectral_mixed[0](N, &A, s) : -1; }
+int launch_spectral_mixed_f32(int N, const PassArgs &A, hipStream_t s) { AnyLib *l = any(); return l && l->launch_spectral_mixed[1] ? l->launch_spectral_mixed[1](N, &A, s) : -1; }
+bool spectral_mixed_supported_f64(int N) { AnyLib *l = any(); return l && l->spectral_mixed_supported[0] && l->spectral_mixed_supported[0](N) != 0; }
+bool spectral_mixed_supported_f32(int N) { AnyLib *l = any(); return l && l->spectral_mixed_supported[1] && l->spectral_mixed_supported[1](N) != 0; }
 }  // namespace dfft

@@ -398,7 +398,9 @@ static int launch_spectral(dfft_plan *p, const Launch &L, const char *in, char *
     if (op.kind >= 3) {      // the factor tables; cy starts at the chunk's first ky row like ay, in complex elements
         A.mcx = op.cx; A.mcy = op.cy ? static_cast<const char *>(op.cy) + L.ty_off * p->esz : nullptr; A.mcz = op.cz;
     }
-    const int r = p->prec == DFFT_F64 ? launch_spectral_f64((int)p->Nx, A, stream) : launch_spectral_f32((int)p->Nx, A, stream);
+    const int N = (int)p->Nx;      // powers of two: this library's kernels; mixed radix (option value 2): libdfft_amd_any.so
+    const int r = is_pow2(p->Nx) ? (p->prec == DFFT_F64 ? launch_spectral_f64(N, A, stream) : launch_spectral_f32(N, A, stream))
+                                 : (p->prec == DFFT_F64 ? launch_spectral_mixed_f64(N, A, stream) : launch_spectral_mixed_f32(N, A, stream));
     if (r == -1) return fail(ERR_UNSUPPORTED, "spectral_op: unsupported x length " + std::to_string(p->Nx));
     if (r != 0) return fail(r, std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)r));
     return 0;
@@ -1071,13 +1073,29 @@ int dfft_init(dfft_plan *p, size_t Nx, size_t Ny, size_t Nz, int P1, int P2, int
     if (p->opt.spectral && (zyx || yzx)) return fail(ERR_UNSUPPORTED, "spectral_layout: pencil and default slab plans only (not the Z_Then_YX / Y_Then_ZX sequences)");
     if (p->opt.spectral && p->opt.spectral != 1) return fail(ERR_ARG, "spectral_layout: 0 = the reference's [Nx][yo][zs], 1 = x-contiguous [yo][zs][Nx]");
     if (p->opt.spectral_op) {
+        if ((zyx || yzx) && p->opt.spectral_op == 2)
+            return fail(ERR_UNSUPPORTED, "spectral_op: no fused chain for the Z_Then_YX / Y_Then_ZX sequences, whatever the x length (" + std::to_string(Nx) +
+                                         " points here): pencil and default slab plans only");
         if (zyx || yzx) return fail(ERR_UNSUPPORTED, "spectral_op: pencil and default slab plans only (not the Z_Then_YX / Y_Then_ZX sequences)");
-        if (p->opt.spectral_op != 1) return fail(ERR_ARG, "spectral_op: 0 or 1");
-        // the fused x pass has the default configuration of the powers of two 2 .. 2048 (csrc/spectral_*.hip); no unfused fallback
+        if (p->opt.spectral_op != 1 && p->opt.spectral_op != 2) return fail(ERR_ARG, "spectral_op: 0, 1 or 2");
+        // the fused x pass has the default configuration of the powers of two 2 .. 2048 (csrc/spectral_*.hip) and, with value 2, the
+        // mixed-radix lengths of csrc/spectral_mixed.inc (kernels of libdfft_amd_any.so); no unfused fallback
         const Axis &ax = p->ax[2];
-        if (ax.bluestein || !is_pow2(Nx) || !(p->prec == DFFT_F64 ? spectral_supported_f64((int)Nx) : spectral_supported_f32((int)Nx)))
-            return fail(ERR_UNSUPPORTED, "spectral_op: an x length of " + std::to_string(Nx) + " points has no fused forward-multiply-inverse kernel "
-                                         "(powers of two from 2 to 2048 on a native chain)");
+        if (ax.bluestein || !is_pow2(Nx) || !(p->prec == DFFT_F64 ? spectral_supported_f64((int)Nx) : spectral_supported_f32((int)Nx))) {
+            if (p->opt.spectral_op == 1)
+                return fail(ERR_UNSUPPORTED, "spectral_op: an x length of " + std::to_string(Nx) + " points has no fused forward-multiply-inverse kernel "
+                                             "(powers of two from 2 to 2048 on a native chain)");
+            const std::string has = " (spectral_op = 2: powers of two from 2 to 2048 and the mixed-radix lengths 2^a 3^b 5^c 7^d up to 2000 that "
+                                    "dfft_spectral_op_supported reports, on a native chain)";
+            if (ax.bluestein)
+                return fail(ERR_UNSUPPORTED, "spectral_op: an x length of " + std::to_string(Nx) + " points runs the Bluestein / two-level kernel in this plan, "
+                                             "which has no fused forward-multiply-inverse form" + has);
+            std::string why;
+            if (!is_pow2(Nx) && !any_spectral_mixed_available(&why))
+                return fail(ERR_UNSUPPORTED, "spectral_op: the fused kernel of an x length of " + std::to_string(Nx) + " points is one of libdfft_amd_any.so: " + why);
+            if (is_pow2(Nx) || !(p->prec == DFFT_F64 ? spectral_mixed_supported_f64((int)Nx) : spectral_mixed_supported_f32((int)Nx)))
+                return fail(ERR_UNSUPPORTED, "spectral_op: an x length of " + std::to_string(Nx) + " points has no fused forward-multiply-inverse kernel" + has);
+        }
         p->worksize_d += p->domainsize;      // the slice that stands in for `out` (forward half) and `in` (inverse half)
     }
     // (one rank: the inverse of an x-contiguous spectrum cannot be the forward launches with conjugation -- their input is the natural grid)
@@ -1359,6 +1377,15 @@ int dfft_exec_c2r(dfft_plan *p, void *out, void *in)
     return 0;
 }
 
+int dfft_spectral_op_supported(int precision, size_t Nx, int option_value)
+{
+    if ((precision != DFFT_F64 && precision != DFFT_F32) || (option_value != 1 && option_value != 2)) return 0;
+    Axis ax;
+    if (!axis_plan(precision, Nx, ax) || ax.bluestein) return 0;      // the x axis of dfft_init with default options
+    if (is_pow2(Nx)) return (precision == DFFT_F64 ? spectral_supported_f64((int)Nx) : spectral_supported_f32((int)Nx)) ? 1 : 0;
+    return option_value == 2 && (precision == DFFT_F64 ? spectral_mixed_supported_f64((int)Nx) : spectral_mixed_supported_f32((int)Nx)) ? 1 : 0;
+}
+
 int dfft_exec_spectral_op(dfft_plan *p, void *out, const void *in, const dfft_spectral_op *op)
 {
     if (p && p->initialized && p->pl.spec.steps.empty())
@@ -1375,7 +1402,9 @@ int dfft_exec_spectral_op(dfft_plan *p, void *out, const void *in, const dfft_sp
     if (sums && (!op->ax || !op->ay || !op->az)) return fail(ERR_ARG, "spectral_op: null multiplier (kinds 1, 2, 4 and 5 need all of ax, ay, az)");
     if (factors && !op->cx && !op->cy && !op->cz) return fail(ERR_ARG, "spectral_op: null multiplier (kinds 3, 4 and 5 need at least one of cx, cy, cz)");
     if (op->kind == 0) {
-        // one tile per workgroup: the kernel adds 32-bit lane offsets (t*MK + l*ME elements) to a scalar base per point
+        // one tile per workgroup: the kernel adds 32-bit lane offsets (t*MK + l*ME elements) to a scalar base per point.  G and the threads
+        // per line are the axis pass's: a configuration of the fused kernel's own (spectral_mixed.inc) has the same G and, at G = 1, no more
+        // threads per line (asserted in spectral_mixed.hip.inc), so the bound holds for it too
         PassInfo pi;
         const Launch *L = p->pl.groups[G_XX].L.empty() ? nullptr : &p->pl.groups[G_XX].L[0];
         if (L && pass_info(p->prec, (int)p->Nx, &pi) && pi.G == 1 &&

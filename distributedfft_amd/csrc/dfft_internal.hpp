@@ -49,6 +49,11 @@ int launch_spectral_f64(int N, const PassArgs &A, hipStream_t stream);
 int launch_spectral_f32(int N, const PassArgs &A, hipStream_t stream);
 bool spectral_supported_f64(int N);
 bool spectral_supported_f32(int N);
+// ... and of the mixed-radix lengths that have one (spectral_mixed.inc; kernels of libdfft_amd_any.so, option spectral_op = 2)
+int launch_spectral_mixed_f64(int N, const PassArgs &A, hipStream_t stream);
+int launch_spectral_mixed_f32(int N, const PassArgs &A, hipStream_t stream);
+bool spectral_mixed_supported_f64(int N);
+bool spectral_mixed_supported_f32(int N);
 #ifdef DFFT_EXPERIMENTS
 int launch_shfl_f32(int N, int dpp, const PassArgs &A, hipStream_t stream);      // LDS-free shuffle pass (A/B only)
 #endif
@@ -56,6 +61,7 @@ int launch_shfl_f32(int N, int dpp, const PassArgs &A, hipStream_t stream);     
 // libdfft_amd_any.so (any_loader.hip): the kernels of every length that is not a power of two up to 8192 -- mixed radix, Bluestein,
 // two-level lines -- loaded at the first plan that needs them.  The launchers of those kernels answer -1 / false while it is missing.
 bool any_available(std::string *why);
+bool any_spectral_mixed_available(std::string *why);      // ... and its fused spectral-operator passes (a library built before they existed lacks them)
 
 void set_error(const std::string &msg);
 

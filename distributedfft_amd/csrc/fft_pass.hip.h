@@ -1159,6 +1159,15 @@ template <typename C> __host__ __device__ __forceinline__ C spectral_factor_line
     return cmul2(cy, cz, ci(cz)) * scale;
 }
 
+// Registers per chunk of the kernel's multiplier loop (E / CH chunks, register c = q * CH + j): four where four divides E -- every power of
+// two from 8 on -- and for a mixed-radix E that it does not divide (10, 18, 30, 50) the largest divisor of E up to 6.  The chunks must cover
+// every register; the host emulation of the mixed-radix lengths (tests/cpp/spectral_mixed_chain_check.hip) walks them with this function.
+template <typename Cfg> constexpr int spectral_chunk()
+{
+    constexpr int E = Cfg::kE;
+    return E < 8 ? E : E % 4 == 0 ? 4 : E % 6 == 0 ? 6 : E % 5 == 0 ? 5 : E % 3 == 0 ? 3 : 2;
+}
+
 // TABLES: 0 = the multiplier is a complex array (PassArgs::mkind 0), 1 = it is built from three real tables (mkind 1, 2), 2 = from three
 // complex tables, with or without the real ones (mkind 3, 4, 5).  Separate instantiations, not a branch: with the array and the table form
 // in one kernel the transformed registers flow through either and the 1024-point fp64 configuration takes 152 VGPRs instead of 128, the
@@ -1194,7 +1203,8 @@ __global__ __launch_bounds__(Cfg::THREADS, spectral_waves<Cfg>()) void fft_spect
     const TilePos<Cfg::kTL> P = tile_pos<Cfg>(A, blk, lwm);
     const R scale = (R)A.mscale;
     C w[E];
-    constexpr int CH = E >= 8 ? 4 : E;
+    constexpr int CH = spectral_chunk<Cfg>();
+    static_assert(E % CH == 0, "the chunks cover every register");
     // a chunk's products are complete before the next chunk's multiplier loads are issued: left to itself the compiler issues all E
     // loads at once (160 VGPRs at 1024 fp64 points, scratch at 2048)
     auto settle = [](C &x) { asm volatile("" : "+v"(x) : : "memory"); };

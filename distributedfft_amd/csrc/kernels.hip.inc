@@ -54,7 +54,11 @@ template <typename Cfg, int TABLES> static int launch_spectral_cfg(const PassArg
     hipLaunchKernelGGL((fft_spectral_kernel<Cfg, TABLES>), dim3(grid), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, A);
     return (int)hipGetLastError();
 }
-#define DFFT_CASE_SPECTRAL(n, v, cfg) case n: return launch_spectral_cfg<cfg, DFFT_PART>(A, stream);
+// (spectral_mixed_<p>.hip has several parts per multiplier form and sets DFFT_SPECTRAL_TABLES itself)
+#ifndef DFFT_SPECTRAL_TABLES
+#define DFFT_SPECTRAL_TABLES DFFT_PART
+#endif
+#define DFFT_CASE_SPECTRAL(n, v, cfg) case n: return launch_spectral_cfg<cfg, DFFT_SPECTRAL_TABLES>(A, stream);
 #define DFFT_CASE_SPECTRAL_OK(n, v, cfg) case n: return true;
 
 // MODE 1 = R2C (ONEPLANE: 0 two-plane split through LDS, 1 one-plane split, 2 split in registers with the conjugate-pair

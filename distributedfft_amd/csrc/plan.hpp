@@ -158,7 +158,7 @@ struct Options {
     int spectral = 0;        // 1: the spectrum is kept x-contiguous, [yo][zs][Nx] (lines along kx natural), instead of the reference's
                              // [Nx][yo][zs]: the forward x pass stores natural lines and the inverse x pass loads them -- neither
                              // touches the point-major layout whose strided read is the slowest pass of every multi-rank plan
-    int spectral_op = 0;     // 1: the plan also builds the fused forward-multiply-inverse chain (Pipeline::spec, group xx) and one more
+    int spectral_op = 0;     // 1 / 2 (2: mixed-radix x lengths as well): the plan also builds the fused forward-multiply-inverse chain (Pipeline::spec, group xx) and one more
                              // work slice for it; 0: nothing of it exists
     int compute_streams = -1; // 2: the pipeline chunks of a pass alternate over two compute streams, so that the drain of chunk c
                              // overlaps the ramp of chunk c + 1 (a chunk launch of 0.1-0.2 ms pays ~20 us of launch / drain / ramp when

@@ -1,6 +1,7 @@
 // spectral_f32.hip -- fft_spectral_kernel (fft_pass.hip.h), f32: the fused forward-multiply-inverse x pass of dfft_exec_spectral_op for the
 // power-of-two lengths 2 .. 2048, each with the default (variant 0) configuration of its length.  Compiled in three parts (-DDFFT_PART =
 // 0: the array multiplier and the entry points, 1: the real table multipliers, 2: the complex factor tables, mkind 3 .. 5).
+// The mixed-radix x lengths of option spectral_op = 2 are spectral_mixed_f32.hip's, in libdfft_amd_any.so.
 #include "cfg_f32.hip.h"
 
 namespace dfft {

@@ -1,0 +1,8 @@
+// spectral_mixed_f32.hip -- fft_spectral_kernel (fft_pass.hip.h), f32: the fused forward-multiply-inverse x pass of dfft_exec_spectral_op for
+// the mixed-radix lengths of spectral_mixed.inc (option spectral_op = 2); kernels of libdfft_amd_any.so.  One object per multiplier form and
+// share of the list (spectral_mixed.hip.inc; the Makefile's NSH_f32 is the number of shares).
+#define DFFT_MIXED_F32
+#define DFFT_SM_P f32
+#define DFFT_SM_LIST DFFT_F32_SPECTRAL_MIXED
+#define DFFT_SM_AXIS F32_M
+#include "spectral_mixed.hip.inc"

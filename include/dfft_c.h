@@ -162,7 +162,8 @@ int dfft_plan_destroy(dfft_plan *plan);
  * lines: two launches per pass and a scratch region in the work area, dfft_axis_plan_info shows the split); a length
  * that does not split that way (a prime above 4096, twice such a prime ...) runs Bluestein's algorithm over a two-level padded
  * length (four launches), so every length from 2 to 2^23 has a plan; beyond 2^24 points per line: ERR_UNSUPPORTED.  c2c = 0: R2C/C2R plan (Nz_out = Nz/2+1,
- * include/params.hpp:30); c2c = 1: complex plan (Nz_out = Nz). */
+ * include/params.hpp:30); c2c = 1: complex plan (Nz_out = Nz).  Option "spectral_op" narrows the x length: 1 = a power of two up to 2048,
+ * 2 = that or a mixed-radix length with a fused kernel (dfft_spectral_op_supported); ERR_UNSUPPORTED otherwise. */
 int dfft_init(dfft_plan *plan, size_t Nx, size_t Ny, size_t Nz, int P1, int P2, int c2c, int allocate);
 /* setWorkArea(void *device, void *host)   mpicufft_pencil_opt1.cpp:329-387.  NULL device =
  * library allocates dfft_work_size_device() bytes. */
@@ -192,12 +193,17 @@ int dfft_get_pipeline_chunks(const dfft_plan *plan);
  *                      plan.  For callers that go forward -> pointwise work on the spectrum -> inverse (the reference's testcase 4,
  *                      tests/src/pencil/random_dist_3D.cu:748-793, does exactly that) and can index through the strides.
  *                      getOutSize / getOutStart / the exchange tables are unchanged.  Pencil and default slab plans, any rank count.
- *   "spectral_op"      0 (default) | 1, before dfft_init: the plan also builds what dfft_exec_spectral_op runs -- forward transform,
+ *   "spectral_op"      0 (default) | 1 | 2, before dfft_init: the plan also builds what dfft_exec_spectral_op runs -- forward transform,
  *                      pointwise multiplier, inverse transform as ONE chain whose forward and inverse x passes are a single launch
  *                      (the spectrum never reaches memory).  It costs one more domain-sized slice of the work area
  *                      (dfft_work_size_device reports it) and nothing else: with 0 no size, launch or chain of the plan differs.  Pencil
  *                      and default slab plans, any rank count, both "spectral_layout" settings, C2C and R2C; the x length must be a power
  *                      of two up to 2048 (dfft_init: ERR_UNSUPPORTED otherwise, and for the Z_Then_YX / Y_Then_ZX sequences).
+ *                      2: everything 1 is, and the x length may also be one of the mixed-radix lengths 2^a 3^b 5^c 7^d <= 2000 that have a
+ *                      fused kernel in libdfft_amd_any.so (384, 768, 1000, 1536, ...: dfft_spectral_op_supported; DESIGN.md lists the few
+ *                      native lengths left out), running the native chain -- ERR_UNSUPPORTED for an x length on the Bluestein or
+ *                      two-level kernel ("native_mixed" = 0, "two_level" = 1, any other length).  A power-of-two x length gives the same
+ *                      plan under 1 and 2.  Any other value: ERR_ARG.
  *   "graph"            1: a single-rank plan replays the kernel launches of an exec as one hipGraph from the second call
  *                      with the same (operation, in, out) on; 0 (default): plain launches -- measured 6-8 us faster per
  *                      exec on ROCm 7.2 (profiles/r2_graph_latency.txt)
@@ -265,7 +271,7 @@ int dfft_enqueue_c2c(dfft_plan *plan, void *out, void *in, int direction);
  *   kind 5  scale * P / (ax[kx] + ay[ky] + az[kz]), and 0 where the sum is 0 (one component of the gradient of a Poisson solution:
  *           cx = i*kx, the sums -|k|^2)
  * cx, cy, cz were appended to the struct: kinds 0 .. 2 never read them, so a caller compiled against the six-field struct stays correct.
- * The plan must have been initialised with option "spectral_op" = 1 (ERR_STATE otherwise).  Blocking, like dfft_exec_r2c; collective on a
+ * The plan must have been initialised with option "spectral_op" = 1 or 2 (ERR_STATE otherwise; 2 admits mixed-radix x lengths).  Blocking, like dfft_exec_r2c; collective on a
  * multi-rank plan.  No phase timing and no hipGraph replay for this chain. */
 typedef struct dfft_spectral_op {
     int32_t kind;           /* 0 array, 1 sum of tables, 2 reciprocal of the sum of tables, 3 product of factor tables, 4 product * sum,
@@ -276,6 +282,9 @@ typedef struct dfft_spectral_op {
     const void *cx, *cy, *cz;   /* kind 3, 4, 5 (read for no other kind) */
 } dfft_spectral_op;
 int dfft_exec_spectral_op(dfft_plan *plan, void *out, const void *in, const dfft_spectral_op *op);
+/* 1 if dfft_init with default options accepts an x length of Nx points under option "spectral_op" = option_value (1 or 2), else 0
+ * (also for another option_value or precision).  Host only: no device is touched; loads libdfft_amd_any.so when Nx is not a power of two. */
+int dfft_spectral_op_supported(int precision, size_t Nx, int option_value);
 
 /* getInSize/getInStart/getOutSize/getOutStart   include/mpicufft_pencil.hpp:112-122
  * (getOutStart returns start_z of the z split -- the reference indexes start_x there, a bug) */

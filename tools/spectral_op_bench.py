@@ -26,7 +26,7 @@ def measure(n, prec, layout, reps, warmup):
     cdt, rdt = (torch.complex128, torch.float64) if prec == "double" else (torch.complex64, torch.float32)
     esz = 16 if prec == "double" else 8
     pl = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), None, precision=prec)
-    pl.setOption("spectral_op", 1)
+    pl.setOption("spectral_op", 1 if n & (n - 1) == 0 else 2)      # 2: the mixed-radix x lengths (768, 1000, ...)
     pl.setOption("spectral_layout", layout)
     pl.initFFT(dfft.GlobalSize(n, n, n), dfft.Pencil_Partition(1, 1), True)
     stream = torch.cuda.current_stream()
