@@ -1,4 +1,5 @@
-// dfft.hip -- plan object, pass descriptors, exec chains and the C ABI of libdfft_amd.so.
+// dfft.hip -- the plan's initialisation (dfft_init), the chain executor with its two sinks, and the C ABI of libdfft_amd.so.  How an
+// axis is planned and how one pass over it is launched is axis.hip; pass descriptors: pipeline.hip; tuners: tune.hip.
 //
 // Host-side counterpart of the reference's decomposition classes; each block cites what it
 // replaces (paths relative to the reference repository):
@@ -8,238 +9,21 @@
 //   execR2C / execC2R        src/pencil/mpicufft_pencil_opt1.cpp:1422-1519 / 1522-1600
 //   slab (P2 == 1)           src/slab/default/mpicufft_slab_opt1.cpp:38-178, 683-783
 //   single rank (fft3d)      src/pencil/mpicufft_pencil_opt1.cpp:132-135, 1434-1436
-#include "../../include/dfft_c.h"
-#include "comm.hpp"
-#include "dfft_internal.hpp"
-#include "fft_pass.hip.h"
-
-#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <complex>
-#include <functional>
 #include <map>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "alloc.hpp"
+#include "axis.hpp"
 #include "host_common.hpp"
-#include "plan.hpp"
 
 namespace dfft {
 
 static thread_local std::string g_error;
 void set_error(const std::string &msg) { g_error = msg; }
-
-static int launch_pass(int prec, int N, int variant, const PassArgs &A, hipStream_t s)
-{
-    PassInfo pi;
-    if (variant && !(prec == DFFT_F64 ? pass_info_f64(N, variant, &pi) : pass_info_f32(N, variant, &pi))) variant = 0;
-    int r = prec == DFFT_F64 ? launch_pass_f64(N, variant, A, s) : launch_pass_f32(N, variant, A, s);
-    if (r == -1) return fail(ERR_UNSUPPORTED, "unsupported line length " + std::to_string(N));
-    if (r != 0) return fail(r, std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)r));
-    return 0;
-}
-static bool pass_info(int prec, int N, PassInfo *pi)
-{
-    return prec == DFFT_F64 ? pass_info_f64(N, 0, pi) : pass_info_f32(N, 0, pi);
-}
-
-#ifdef DFFT_EXPERIMENTS
-// A/B build only (make exp): DFFT_EXP_F32_TWIDDLES=1 rounds every fp64 table -- tw, twN, tw_zr (make_twiddles), the Bluestein chirp
-// and bhat (upload_complex) -- through fp32: the defect the per-entry forward bound of tests/parity_metric.py has to catch
-// (profiles/r6_f32_twiddle_proof.txt, profiles/entry_parity_mutation.txt); the shipped library has no such switch
-static const bool f32_tw = [] { const char *e = getenv("DFFT_EXP_F32_TWIDDLES"); return e && atoi(e) != 0; }();
-#else
-constexpr bool f32_tw = false;
-#endif
-
-// twiddle table exp(-2*pi*i*j/N), evaluated in long double, rounded once
-static int make_twiddles(int prec, size_t N, void **dev)
-{
-    const long double PI = 3.141592653589793238462643383279502884L;
-    const size_t esz = prec == DFFT_F64 ? 16 : 8;
-    std::vector<char> host(esz * N);
-    for (size_t j = 0; j < N; j++) {
-        long double a = -2.0L * PI * (long double)j / (long double)N;
-        if (prec == DFFT_F64) {
-            double *d = reinterpret_cast<double *>(host.data()) + 2 * j;
-            d[0] = (double)cosl(a); d[1] = (double)sinl(a);
-            if (f32_tw) { d[0] = (double)(float)d[0]; d[1] = (double)(float)d[1]; }
-        } else {
-            float *d = reinterpret_cast<float *>(host.data()) + 2 * j;
-            d[0] = (float)cosl(a); d[1] = (float)sinl(a);
-        }
-    }
-    HIP_TRY(hipMalloc(dev, esz * N));
-    HIP_TRY(hipMemcpy(*dev, host.data(), esz * N, hipMemcpyHostToDevice));
-    return 0;
-}
-
-
-
-static void host_fft_pow2(std::vector<std::complex<long double>> &a)
-{
-    const long double PI = 3.141592653589793238462643383279502884L;
-    const size_t n = a.size();
-    for (size_t i = 1, j = 0; i < n; i++) {
-        size_t bit = n >> 1;
-        for (; j & bit; bit >>= 1) j ^= bit;
-        j ^= bit;
-        if (i < j) std::swap(a[i], a[j]);
-    }
-    for (size_t len = 2; len <= n; len <<= 1) {
-        for (size_t i = 0; i < n; i += len)
-            for (size_t k = 0; k < len / 2; k++) {
-                long double ang = -2.0L * PI * (long double)k / (long double)len;
-                std::complex<long double> w(cosl(ang), sinl(ang));
-                auto u = a[i + k], v = a[i + k + len / 2] * w;
-                a[i + k] = u + v;
-                a[i + k + len / 2] = u - v;
-            }
-    }
-}
-
-static int upload_complex(int prec, const std::vector<std::complex<long double>> &h, void **dev)
-{
-    const size_t esz = prec == DFFT_F64 ? 16 : 8;
-    std::vector<char> buf(esz * h.size());
-    for (size_t j = 0; j < h.size(); j++) {
-        if (prec == DFFT_F64) {
-            double *d = reinterpret_cast<double *>(buf.data()) + 2 * j;
-            d[0] = (double)h[j].real(); d[1] = (double)h[j].imag();
-            if (f32_tw) { d[0] = (double)(float)d[0]; d[1] = (double)(float)d[1]; }
-        } else {
-            float *d = reinterpret_cast<float *>(buf.data()) + 2 * j;
-            d[0] = (float)h[j].real(); d[1] = (float)h[j].imag();
-        }
-    }
-    HIP_TRY(hipMalloc(dev, buf.size()));
-    HIP_TRY(hipMemcpy(*dev, buf.data(), buf.size(), hipMemcpyHostToDevice));
-    return 0;
-}
-
-static void axis_free(Axis &a)
-{
-    for (void **t : {&a.tw, &a.chirp, &a.bhat, &a.twN}) if (*t) { (void)hipFree(*t); *t = nullptr; }
-    for (auto &l : a.lv) axis_free(l);
-}
-
-// Two-level plan of an axis: N = N1*N2 with both factors within reach of the generic kernel -- a power of two up to 8192 (plain
-// chain) or any length F with a Bluestein inner transform of next_pow2(2F-1) <= 8192 points.  The cheapest split by a model of
-// the launches' cost in passes over the data: plain 1 (2 on the sub-tile workgroups of 4096 / 8192 points), Bluestein 1.5 plus
-// the padding ratio M/F.  Largest N: 2^24 (32-bit point indices in the kernel).
-static bool axis_plan_two_level(int prec, size_t N, Axis &a)
-{
-    a.N = N;
-    if (N < 4 || N > ((size_t)1 << 24)) return false;
-    PassInfo pi;
-    auto level_cost = [&](size_t F, bool &blue, size_t &M) -> double {
-        if (is_pow2(F) && F <= 8192 && pass_info(prec, (int)F, &pi)) { blue = false; M = F; return F > 2048 ? 2.0 : 1.0; }
-        M = next_pow2(2 * F - 1);
-        if (F < 2 || M > 8192 || !pass_info(prec, (int)M, &pi)) return -1.0;
-        blue = true;
-        return 1.5 + (double)M / (double)F + (M > 2048 ? 2.0 : 0.0);
-    };
-    double best = -1.0;
-    size_t b1 = 0;
-    for (size_t n1 = 2; n1 * n1 <= N; n1++) {
-        if (N % n1) continue;
-        for (size_t f : {n1, N / n1}) {
-            bool bl1, bl2; size_t m1, m2;
-            const double c1 = level_cost(f, bl1, m1), c2 = level_cost(N / f, bl2, m2);
-            if (c1 < 0 || c2 < 0) continue;
-            // ties: the smaller largest inner transform, then the longer second level (its scratch reads are contiguous)
-            const double c = c1 + c2 + 1e-6 * (double)std::max(m1, m2) + (f > N / f ? 1e-9 : 0.0);
-            if (best < 0 || c < best) { best = c; b1 = f; }
-        }
-    }
-    if (best < 0) return false;
-    a.two = true; a.bluestein = true; a.M = 0;
-    a.lv.assign(2, Axis());
-    const size_t f[2] = {b1, N / b1};
-    for (int k = 0; k < 2; k++) {
-        bool bl; size_t M;
-        level_cost(f[k], bl, M);
-        a.lv[k].N = f[k]; a.lv[k].bluestein = bl; a.lv[k].M = M;
-    }
-    return true;
-}
-
-// Long Bluestein plan: any length up to 2^23 whose padded length M = next_pow2(2N - 1) <= 2^24 runs as a two-level line
-static bool axis_plan_long(int prec, size_t N, Axis &a)
-{
-    a = Axis();
-    a.N = N;
-    if (N < 2) return false;
-    const size_t M = next_pow2(2 * N - 1);
-    if (M > ((size_t)1 << 24)) return false;
-    Axis inner;
-    if (!axis_plan_two_level(prec, M, inner)) return false;
-    a.longb = true; a.bluestein = true; a.two = false; a.M = M;
-    a.lv.assign(1, inner);
-    return true;
-}
-
-// decide how an axis of length N is transformed; returns false if unsupported.  two_level: 0 = only lengths with no other
-// plan, 1 = wherever a split exists (tests, A/B runs)
-static bool axis_plan(int prec, size_t N, Axis &a, bool mixed = true, int two_level = 0)
-{
-    PassInfo pi;
-    a.N = N;
-    if (two_level == 1 && axis_plan_two_level(prec, N, a)) return true;
-    // native chain: powers of two 2..8192 and the mixed-radix lengths of kernels_mixed.inc (2^a 3^b 5^c 7^d <= 2048)
-    if ((is_pow2(N) || mixed) && N <= 8192 && pass_info(prec, (int)N, &pi)) { a.bluestein = false; a.M = N; return true; }
-    const size_t M = next_pow2(2 * N - 1);
-    if (N < 2 || M > 8192 || !pass_info(prec, (int)M, &pi)) return axis_plan_two_level(prec, N, a) || axis_plan_long(prec, N, a);
-    a.bluestein = true; a.M = M;
-    return true;
-}
-
-// Bluestein even for a power of two: its kernel is the one with a strided real-line load (Y_Then_ZX) and the real modes;
-// lengths beyond its reach in two levels (the generic kernel again, real modes included)
-static bool axis_plan_bluestein(int prec, size_t N, Axis &a, int two_level = 0)
-{
-    PassInfo pi;
-    a.N = N;
-    if (two_level == 1 && axis_plan_two_level(prec, N, a)) return true;
-    const size_t M = next_pow2(2 * N - 1);
-    if (N < 2 || M > 8192 || !pass_info(prec, (int)M, &pi)) return axis_plan_two_level(prec, N, a) || axis_plan_long(prec, N, a);
-    a.bluestein = true; a.M = M;
-    return true;
-}
-
-static int axis_upload(int prec, Axis &a)
-{
-    const long double PI = 3.141592653589793238462643383279502884L;
-    if (a.two) {
-        for (auto &l : a.lv) TRY(axis_upload(prec, l));
-        if (!a.twN) TRY(make_twiddles(prec, a.N, &a.twN));
-        return 0;
-    }
-    if (a.longb) TRY(axis_upload(prec, a.lv[0]));
-    else if (!a.tw) TRY(make_twiddles(prec, a.M, &a.tw));
-    if (a.bluestein && !a.chirp) {
-        const size_t N = a.N, M = a.M;
-        std::vector<std::complex<long double>> ch(N), b(M, std::complex<long double>(0, 0));
-        for (size_t n = 0; n < N; n++) {
-            const size_t q = (size_t)(((unsigned __int128)n * n) % (2 * N));      // n^2 mod 2N keeps the angle exact
-            const long double ang = PI * (long double)q / (long double)N;
-            ch[n] = std::complex<long double>(cosl(ang), -sinl(ang));           // exp(-i pi n^2 / N)
-            b[n] = std::conj(ch[n]);
-            if (n) b[M - n] = std::conj(ch[n]);
-        }
-        host_fft_pow2(b);
-        for (auto &v : b) v /= (long double)M;
-        TRY(upload_complex(prec, ch, &a.chirp));
-        TRY(upload_complex(prec, b, &a.bhat));
-    }
-    return 0;
-}
 
 }  // namespace dfft
 
@@ -252,95 +36,6 @@ static void fill_tables(dfft_plan *p, const Launch &L, PassArgs &A)
     A.lnseg = L.lseg.nseg; A.snseg = L.sseg.nseg;
     A.ltab = L.lent == SIZE_MAX ? nullptr : reinterpret_cast<const SegEntry *>(static_cast<const char *>(p->tables_d) + L.lent);
     A.stab = L.sent == SIZE_MAX ? nullptr : reinterpret_cast<const SegEntry *>(static_cast<const char *>(p->tables_d) + L.sent);
-}
-
-// one launch of the generic kernel for the lines (or sub-lines) of `ax`: plain chain or Bluestein
-static int launch_generic(int prec, const Axis &ax, PassArgs &A, hipStream_t s)
-{
-    A.tw = ax.tw; A.tw2 = ax.chirp; A.tw3 = ax.bhat; A.NL = (uint32_t)ax.N; A.plain = ax.bluestein ? 0 : 1;
-    return prec == DFFT_F64 ? launch_bluestein_f64((int)ax.M, A, s) : launch_bluestein_f32((int)ax.M, A, s);
-}
-
-// two-level line (fft_pass.hip.h): level 1 through the pass's load form into the scratch, level 2 from the scratch through its
-// store form.  real_mode / NK as for a one-launch generic pass.
-static int launch_two_level(int prec, const Axis &ax, PassArgs A, int real_mode, size_t NK, void *scratch, int TL, hipStream_t s)
-{
-    A.lvN = (uint32_t)ax.N; A.lvNK = (uint32_t)NK; A.NK = (uint32_t)NK; A.real_mode = real_mode; A.lvtw = ax.twN; A.lvw = scratch;
-    // lanes over the lines of a tile, or over neighbouring sub-lines of one line where the level's outer side has natural lines;
-    // the scratch layout that keeps both levels in runs (fft_pass.hip.h)
-    const bool q1 = A.load_kind == LOAD_LINES, q2 = A.store_kind == STORE_LINES;
-    const uint32_t N1 = (uint32_t)ax.lv[0].N, N2 = (uint32_t)ax.lv[1].N;
-    if (!q1 && !q2) { A.lvlay = 0; A.lvs1 = N2 * (uint32_t)TL; A.lvs2 = (uint32_t)TL; }
-    else if (q1) { A.lvlay = 1; A.lvs1 = N2; A.lvs2 = 1; }
-    else { A.lvlay = 1; A.lvs1 = 1; A.lvs2 = N1; }
-    for (int level = 1; level <= 2; level++) {
-        PassArgs B = A;
-        B.lv = level; B.lvQ = (uint32_t)ax.lv[2 - level].N; B.lvqm = level == 1 ? q1 : q2;
-        const int r = launch_generic(prec, ax.lv[level - 1], B, s);
-        if (r != 0) return fail(r == -1 ? ERR_UNSUPPORTED : r, "two-level pass launch failed for length " + std::to_string(ax.N));
-    }
-    return 0;
-}
-
-// bytes of scratch a two-level launch needs
-static size_t two_level_bytes(const PassArgs &A, int TL, size_t N, size_t esz) { return (size_t)A.ntiles * (size_t)TL * N * esz; }
-
-// Long Bluestein pass (fft_pass.hip.h, PassArgs::lb): X = ch * IFFT_M(FFT_M(x * ch, zero-padded) * bhat), the two M-point transforms
-// as two-level lines.  Launch 1 reads the pass's own load form (chirp and padding on the fly), launch 4 writes its own store form
-// (chirp on the fly), so unpack / pack / transposes stay fused as for every other pass; between them the line lives in a scratch of
-// natural M-point lines (S2) and the two-level scratch (S1).  The inverse M-point transform is the forward one between re <-> im
-// swaps; an inverse PASS swaps at its own two ends (PassArgs::swap of launches 1 and 4) like every inverse pass.
-//   1  level 1, pass's load form -> S1   lb = 1: x[n] * ch[n], 0 beyond the line          2  level 2, S1 -> S2 natural, * bhat, swapped
-//   3  level 1, S2 natural -> S1                                                           4  level 2, S1 -> pass's store form: swap, * ch
-static size_t long_bytes(const PassArgs &A, int TL, size_t M, size_t esz) { return 2 * (size_t)A.ntiles * (size_t)TL * M * esz; }
-static int launch_long_bluestein(int prec, const Axis &ax, const PassArgs &P, int real_mode, size_t NK, void *scratch, int TL, hipStream_t s)
-{
-    const Axis &in = ax.lv[0];      // the two-level plan of M
-    const uint32_t M = (uint32_t)ax.M, N1 = (uint32_t)in.lv[0].N, N2 = (uint32_t)in.lv[1].N;
-    const size_t esz = prec == DFFT_F64 ? 16 : 8;
-    char *S1 = static_cast<char *>(scratch), *S2 = S1 + (size_t)P.ntiles * (size_t)TL * M * esz;
-    auto level = [&](PassArgs B, int lv, bool qm) {
-        B.lvN = M; B.lvNK = M; B.lvtw = in.twN; B.lvw = S1; B.lv = lv; B.lvQ = (uint32_t)in.lv[2 - lv].N; B.lvqm = qm ? 1 : 0;
-        const int r = launch_generic(prec, in.lv[lv - 1], B, s);
-        return r == 0 ? 0 : fail(r == -1 ? ERR_UNSUPPORTED : r, "long Bluestein launch failed for length " + std::to_string(ax.N));
-    };
-    auto layout = [&](PassArgs &B, bool q1, bool q2) {      // as launch_two_level
-        if (!q1 && !q2) { B.lvlay = 0; B.lvs1 = N2 * (uint32_t)TL; B.lvs2 = (uint32_t)TL; }
-        else if (q1) { B.lvlay = 1; B.lvs1 = N2; B.lvs2 = 1; }
-        else { B.lvlay = 1; B.lvs1 = 1; B.lvs2 = N1; }
-    };
-    // natural M-point lines in S2 for the same tiles
-    auto natural_side = [&](PassArgs &B, bool store) {
-        if (store) { B.store_kind = STORE_LINES; B.out = S2; B.KS_out = 0; B.AS_out = 0; B.stab = nullptr; B.sseg = nullptr; B.snseg = 0; B.suni = 0; B.shift = 0; }
-        else { B.load_kind = LOAD_LINES; B.in = S2; B.KS_in = 0; B.AS_in = 0; B.ltab = nullptr; B.lseg = nullptr; B.lnseg = 0; B.luni = 0; }
-    };
-    const bool qin = P.load_kind == LOAD_LINES, qout = P.store_kind == STORE_LINES;      // (as launch_two_level decides)
-    {   // forward M-point transform: pass's load form -> S2
-        PassArgs A = P;
-        A.shift = 0;
-        natural_side(A, true);
-        layout(A, qin, true);
-        PassArgs L1 = A;
-        L1.lb = 1; L1.lbL = (uint32_t)ax.N; L1.lbK = (uint32_t)NK; L1.lbtab = ax.chirp; L1.real_mode = real_mode;      // (swap: the pass's)
-        TRY(level(L1, 1, qin));
-        PassArgs L2 = A;
-        L2.lb = 2; L2.lbL = M; L2.lbK = M; L2.lbtab = ax.bhat; L2.real_mode = 0; L2.swap = 1;
-        TRY(level(L2, 2, true));
-    }
-    {   // inverse M-point transform: S2 -> pass's store form
-        PassArgs A = P;
-        natural_side(A, false);
-        layout(A, true, qout);
-        PassArgs L3 = A;
-        L3.lb = 0; L3.real_mode = 0; L3.swap = 0; L3.shift = 0;
-        natural_side(L3, true);      // (its store side is the scratch S1: unused, but must not carry the pass's tables)
-        L3.out = nullptr;
-        TRY(level(L3, 1, true));
-        PassArgs L4 = A;
-        L4.lb = 6; L4.lbL = (uint32_t)ax.N; L4.lbK = (uint32_t)NK; L4.lbtab = ax.chirp; L4.real_mode = real_mode;      // (swap: the pass's)
-        TRY(level(L4, 2, qout));
-    }
-    return 0;
 }
 
 // the launches of one group on axis `axis` (0 = z, 1 = y, 2 = x) in line form `form` (LineForm); conj: with conjugation
@@ -361,26 +56,12 @@ static int launch(dfft_plan *p, const Launch &L, int form, int axis, bool conj, 
         A.tw2 = p->tw_zr;
         const bool z = form != FORM_REAL_LINES;
         const int M = (int)((z ? p->Nz : p->Ny) / 2), variant = z ? p->opt.real_variant : 0;
-        const int r = p->prec == DFFT_F64 ? launch_real_f64(M, real_mode, variant, A, stream) : launch_real_f32(M, real_mode, variant, A, stream);
+        const int r = kernels(p->prec).launch_real(M, real_mode, variant, A, stream);
         if (r != 0) return fail(r == -1 ? ERR_UNSUPPORTED : r, "real pass launch failed for length " + std::to_string(2 * M));
         return 0;
     }
-    if (!ax.bluestein) {
-        if (real_mode) return fail(ERR_UNSUPPORTED, "real pass without a packed or Bluestein plan");      // (dfft_init rules this out)
-        return launch_pass(p->prec, (int)ax.N, form == FORM_FWD ? p->vfwd[axis] : form == FORM_INV ? p->vinv[axis] : 0, A, stream);
-    }
-    if (ax.longb) {
-        if (long_bytes(A, p->TL, ax.M, p->esz) > p->lv_bytes) return fail(ERR_STATE, "long Bluestein pass: scratch region too small");
-        return launch_long_bluestein(p->prec, ax, A, real_mode, NK, static_cast<char *>(p->work_d) + p->lv_off, p->TL, stream);
-    }
-    if (ax.two) {
-        if (two_level_bytes(A, p->TL, ax.N, p->esz) > p->lv_bytes) return fail(ERR_STATE, "two-level pass: scratch region too small");
-        return launch_two_level(p->prec, ax, A, real_mode, NK, static_cast<char *>(p->work_d) + p->lv_off, p->TL, stream);
-    }
-    A.NK = (uint32_t)NK; A.real_mode = real_mode;
-    const int r = launch_generic(p->prec, ax, A, stream);
-    if (r != 0) return fail(r == -1 ? ERR_UNSUPPORTED : r, "Bluestein pass launch failed for length " + std::to_string(ax.N));
-    return 0;
+    const int variant = form == FORM_FWD ? p->vfwd[axis] : form == FORM_INV ? p->vinv[axis] : 0;
+    return launch_axis(p->prec, ax, A, variant, real_mode, NK, static_cast<char *>(p->work_d) + p->lv_off, p->lv_bytes, p->TL, stream);
 }
 
 // one launch of group xx (fft_spectral_kernel): forward x pass, the multiplier p->op, inverse x pass
@@ -398,9 +79,9 @@ static int launch_spectral(dfft_plan *p, const Launch &L, const char *in, char *
     if (op.kind >= 3) {      // the factor tables; cy starts at the chunk's first ky row like ay, in complex elements
         A.mcx = op.cx; A.mcy = op.cy ? static_cast<const char *>(op.cy) + L.ty_off * p->esz : nullptr; A.mcz = op.cz;
     }
-    const int N = (int)p->Nx;      // powers of two: this library's kernels; mixed radix (option value 2): libdfft_amd_any.so
-    const int r = is_pow2(p->Nx) ? (p->prec == DFFT_F64 ? launch_spectral_f64(N, A, stream) : launch_spectral_f32(N, A, stream))
-                                 : (p->prec == DFFT_F64 ? launch_spectral_mixed_f64(N, A, stream) : launch_spectral_mixed_f32(N, A, stream));
+    // powers of two: this library's kernels; mixed radix (option value 2): libdfft_amd_any.so -- as dfft_init found (spectral_kernel_for)
+    const Kernels &K = kernels(p->prec);
+    const int r = (p->spectral_kernel == SPECTRAL_CORE ? K.launch_spectral : K.launch_spectral_mixed)((int)p->Nx, A, stream);
     if (r == -1) return fail(ERR_UNSUPPORTED, "spectral_op: unsupported x length " + std::to_string(p->Nx));
     if (r != 0) return fail(r, std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)r));
     return 0;
@@ -444,7 +125,6 @@ static int exchange(dfft_plan *p, int which, bool forward, const void *send, voi
     return exchange_tables(p, which, T, forward, static_cast<const char *>(send), static_cast<char *>(recv), p->stream, 0,
                            16 + 2 * (uint64_t)which + (forward ? 1 : 0));
 }
-
 
 // ---- per-phase timing: (start, stop) event pairs on whatever stream the work runs on --------
 static int span_begin(dfft_plan *p, int phase, hipStream_t s)
@@ -891,8 +571,8 @@ int dfft_plan_create(dfft_plan **plan, int kind, int precision, const dfft_confi
     // (src/mpicufft.cpp:46-51); here ranks beyond it simply may not create plans.
     if (max_world_size > 0 && max_world_size < p->nranks) p->nranks = max_world_size;
     if (p->rank < 0 || p->rank >= p->nranks) { delete p; return fail(ERR_ARG, "rank outside the world"); }
-    p->esz = precision == DFFT_F64 ? 16 : 8;
-    p->TL = precision == DFFT_F64 ? TL_F64 : TL_F32;
+    p->esz = kernels(precision).esz;
+    p->TL = kernels(precision).TL;
     env_defaults(p->opt);
     *plan = p;
     return 0;
@@ -960,6 +640,106 @@ int dfft_plan_destroy(dfft_plan *p)
     return 0;
 }
 
+// axis plans: native chain (powers of two 2..8192, mixed-radix lengths up to 2048) or Bluestein (any length with 2N-1 <= 8192)
+static int plan_axes(dfft_plan *p, size_t Nx, size_t Ny, size_t Nz, bool c2c, bool yzx)
+{
+    Axis az, ay, axx;
+    const bool mixed = p->opt.native_mixed != 0;
+    // packed real z pass: Nz/2-point complex transform + Hermitian split / merge (powers of two, and even lengths whose
+    // half has a mixed-radix configuration)
+    const int tl = p->opt.two_level;      // 1: two-level lines wherever a split exists (the packed real kernels then stand back)
+    const bool zr_native = !yzx && !c2c && tl != 1 && Nz >= 4 && Nz <= 4096 && Nz % 2 == 0 && (is_pow2(Nz) || mixed) &&
+                           kernels(p->prec).real_supported((int)(Nz / 2));
+    const size_t zlen = zr_native ? Nz / 2 : Nz;
+    // Y_Then_ZX, R2C: the y pass reads real lines in place, which only the Bluestein kernel does
+    // Y_Then_ZX, R2C: the y pass reads real lines in place.  Power-of-two Ny: the packed Ny/2-point real kernel
+    // with its strided-line load; any other Ny: the Bluestein kernel's real mode (Ny <= 4096)
+    const bool yr_native = yzx && !c2c && tl != 1 && is_pow2(Ny) && Ny >= 4 && Ny <= 2048;
+    const bool yok = yr_native ? axis_plan(p->prec, Ny / 2, ay) : yzx && !c2c ? axis_plan_bluestein(p->prec, Ny, ay, tl) : axis_plan(p->prec, Ny, ay, mixed, tl);
+    // a real z pass is either the packed Nz/2-point kernel or the Bluestein kernel's real modes: never
+    // the plain complex chain (Nz == 2 would otherwise pick it and launch Bluestein without its tables)
+    const bool zreal_generic = !yzx && !c2c && !zr_native;
+    const bool zok = zreal_generic ? axis_plan_bluestein(p->prec, Nz, az, tl) : axis_plan(p->prec, zlen, az, mixed, tl);
+    if (!zok || !yok || !axis_plan(p->prec, Nx, axx, mixed, tl))
+        return fail(ERR_UNSUPPORTED, "unsupported axis length (every length from 2 to 2^23 has a plan; beyond that only lengths N1*N2 <= 2^24 whose "
+                                     "factors are each a power of two up to 8192 or any length up to 4096)");
+    // an axis outside the power-of-two kernels of this library runs kernels of libdfft_amd_any.so (any_loader.hip): no fallback
+    for (const Axis *a : {&az, &ay, &axx}) {
+        std::string why;
+        if ((a->bluestein || !is_pow2(a->N)) && !any_available(&why))
+            return fail(ERR_UNSUPPORTED, "an axis of " + std::to_string(a->N) + " points needs the kernels of libdfft_amd_any.so (every length that is "
+                                         "not a power of two up to 8192): " + why);
+    }
+    for (auto &a : p->ax) axis_free(a);
+    p->ax[0] = az; p->ax[1] = ay; p->ax[2] = axx;
+    p->zreal_native = zr_native;
+    p->yreal_native = yr_native;
+    return 0;
+}
+
+// option spectral_op: the plans that have the fused chain, and the fused x kernel the plan's x axis runs (p->spectral_kernel)
+static int admit_spectral_op(dfft_plan *p, bool sequence)
+{
+    if (sequence && p->opt.spectral_op == 2)
+        return fail(ERR_UNSUPPORTED, "spectral_op: no fused chain for the Z_Then_YX / Y_Then_ZX sequences, whatever the x length (" + std::to_string(p->Nx) +
+                                     " points here): pencil and default slab plans only");
+    if (sequence) return fail(ERR_UNSUPPORTED, "spectral_op: pencil and default slab plans only (not the Z_Then_YX / Y_Then_ZX sequences)");
+    if (p->opt.spectral_op != 1 && p->opt.spectral_op != 2) return fail(ERR_ARG, "spectral_op: 0, 1 or 2");
+    std::string why;
+    p->spectral_kernel = spectral_kernel_for(p->prec, p->ax[2], p->opt.spectral_op, &why);
+    return p->spectral_kernel == SPECTRAL_NONE ? fail(ERR_UNSUPPORTED, why) : 0;
+}
+
+// kernel configuration per pass, by role (PassRole); lengths without a configuration for a role use the default
+static void choose_pass_roles(dfft_plan *p)
+{
+    auto has = [&](const Axis &a, int role) { return has_variant(p->prec, a, role); };
+    for (int k = 0; k < 3; k++) p->vfwd[k] = p->vinv[k] = ROLE_DEFAULT;
+    if (p->prec == DFFT_F64) {
+        // the multi-rank inverse x pass reads the point-major API layout: 16 lines x 32 points (256-byte runs) -- where the rows
+        // are whole tiles.  On the 513-wide rows of an R2C plan the 256-byte runs straddle three cache lines and the one
+        // workgroup per CU re-reads 17 % of them (profiles/r3_pmc_traffic_f64_r2c.json): the default configuration (8 lines,
+        // two workgroups per CU) is 15 % faster there, 3.66 vs 4.26 ms at 1024^3 (profiles/r3_strided_read_odd_pitch.txt)
+        const size_t zs_local = p->zs.empty() ? p->Nzc : p->zs[p->zyx ? (size_t)p->rank % p->zs.size() : (size_t)p->pj % p->zs.size()];
+        if (has(p->ax[2], ROLE_STRIDED_READ) && zs_local % (size_t)p->TL == 0) p->vinv[2] = ROLE_STRIDED_READ;
+        // ... and without a second exchange (P1 = 1) its persistent form with stores and loads fused (8.27 -> 7.64 ms at 1024^3,
+        // profiles/r4_persist3.txt); launches that do not have its pair of address forms run ROLE_STRIDED_READ by themselves
+        if (p->vinv[2] == ROLE_STRIDED_READ && p->P1 == 1 && has(p->ax[2], ROLE_STRIDED_READ_FUSED)) p->vinv[2] = ROLE_STRIDED_READ_FUSED;
+        // complex z passes have natural lines on one side and long-run stores
+        const int zrole = has(p->ax[0], ROLE_LINES) ? ROLE_LINES : has(p->ax[0], ROLE_STREAM) ? ROLE_STREAM : ROLE_DEFAULT;
+        if (p->c2c) p->vfwd[0] = p->vinv[0] = zrole;
+        // the inverse y pass stores tiled-transpose chunks (1 KiB runs)
+        if (has(p->ax[1], ROLE_STREAM)) p->vinv[1] = ROLE_STREAM;
+        if (p->opt.spectral) {      // x passes with natural lines on one side, like the complex z passes
+            const int xrole = has(p->ax[2], ROLE_LINES) ? ROLE_LINES : has(p->ax[2], ROLE_STREAM) ? ROLE_STREAM : ROLE_DEFAULT;
+            p->vfwd[2] = p->vinv[2] = xrole;
+        }
+    } else {
+        if (p->c2c && has(p->ax[0], ROLE_NATURAL_LOAD)) p->vfwd[0] = ROLE_NATURAL_LOAD;
+        if (p->c2c && has(p->ax[0], ROLE_NATURAL_STORE)) p->vinv[0] = ROLE_NATURAL_STORE;
+        for (int ax = 1; ax <= 2; ax++)
+            if (has(p->ax[ax], ROLE_TILED)) p->vfwd[ax] = p->vinv[ax] = ROLE_TILED;
+        // the inverse y pass of a multi-rank plan stores transposed tiles: whole-line stores (ROLE_TRANSPOSED_STORE) where the length
+        // has such a configuration (2048 points: 4.80 -> 3.63 ms on rank 0 of 2 x 4 at 2048^3)
+        // (a single rank's complex inverse runs the forward launches: there vinv is not used)
+        if (has(p->ax[1], ROLE_TRANSPOSED_STORE)) p->vinv[1] = ROLE_TRANSPOSED_STORE;
+        // 2048 points and more on a multi-rank plan: the forward y pass and the inverse x pass (the strided read of the API layout)
+        // run the streaming sibling of the tiled configuration -- what dfft_tune_variants picked on every 2048^3 plan measured
+        // (rank 0 of 2 x 4: y 4.93 -> 3.78 ms, x^-1 5.36 -> 4.46; of 8 x 1 the same two; profiles/r5_tuner_choices.txt).  The
+        // forward x pass and the inverse y pass lose with it (round 3), shorter lines were not measured: they keep their rule.
+        if (p->nranks > 1 && p->ax[1].N >= 2048 && has(p->ax[1], ROLE_TILED_STREAM)) p->vfwd[1] = ROLE_TILED_STREAM;
+        if (p->nranks > 1 && p->ax[2].N >= 2048 && has(p->ax[2], ROLE_TILED_STREAM)) p->vinv[2] = ROLE_TILED_STREAM;
+        if (p->opt.spectral) {      // x-contiguous spectrum: the forward x pass stores natural lines like the inverse z pass
+            if (has(p->ax[2], ROLE_NATURAL_STORE)) p->vfwd[2] = ROLE_NATURAL_STORE;
+            // ... and its inverse loads them: point fastest for the first pass only, the same-tile stores stay line fastest
+            if (has(p->ax[2], ROLE_NATURAL_LOAD_TILED_STORE)) p->vinv[2] = ROLE_NATURAL_LOAD_TILED_STORE;
+        }
+        // (The inverse y pass stores transposed tiles, which a line-fastest fp32 wave -- 16 lines x 4 points -- writes in 32-byte
+        // pieces.  A point-fastest store mapping, PassCfg::MAP = 2, writes whole lines and was measured: 1024 points 4.42 vs 4.30 ms,
+        // 2048 points 10.55 vs 10.35, no better -- L2 merges the pieces; profiles/r3_f32_inverse_y_point_fastest_store.txt.)
+    }
+}
+
 int dfft_init(dfft_plan *p, size_t Nx, size_t Ny, size_t Nz, int P1, int P2, int c2c, int allocate)
 {
     if (!p) return fail(ERR_ARG, "null plan");
@@ -977,40 +757,7 @@ int dfft_init(dfft_plan *p, size_t Nx, size_t Ny, size_t Nz, int P1, int P2, int
     const bool zyx = zyx_kind && P1 > 1;
     if (P1 > MAXSEG || P2 > MAXSEG) return fail(ERR_UNSUPPORTED, "more than 32 ranks per exchange group");
     if ((size_t)P1 > Nx || (!zyx && (size_t)P1 > Ny) || (size_t)P2 > Ny) return fail(ERR_ARG, "partition larger than the grid");
-    // axis plans: native chain (powers of two 2..8192, mixed-radix lengths up to 2048) or Bluestein (any length with 2N-1 <= 8192)
-    {
-        Axis az, ay, axx;
-        const bool mixed = p->opt.native_mixed != 0;
-        // packed real z pass: Nz/2-point complex transform + Hermitian split / merge (powers of two, and even lengths whose
-        // half has a mixed-radix configuration)
-        const int tl = p->opt.two_level;      // 1: two-level lines wherever a split exists (the packed real kernels then stand back)
-        const bool zr_native = !yzx && !c2c && tl != 1 && Nz >= 4 && Nz <= 4096 && Nz % 2 == 0 && (is_pow2(Nz) || mixed) &&
-                               (p->prec == DFFT_F64 ? real_supported_f64((int)(Nz / 2)) : real_supported_f32((int)(Nz / 2)));
-        const size_t zlen = zr_native ? Nz / 2 : Nz;
-        // Y_Then_ZX, R2C: the y pass reads real lines in place, which only the Bluestein kernel does
-        // Y_Then_ZX, R2C: the y pass reads real lines in place.  Power-of-two Ny: the packed Ny/2-point real kernel
-        // with its strided-line load; any other Ny: the Bluestein kernel's real mode (Ny <= 4096)
-        const bool yr_native = yzx && !c2c && tl != 1 && is_pow2(Ny) && Ny >= 4 && Ny <= 2048;
-        const bool yok = yr_native ? axis_plan(p->prec, Ny / 2, ay) : yzx && !c2c ? axis_plan_bluestein(p->prec, Ny, ay, tl) : axis_plan(p->prec, Ny, ay, mixed, tl);
-        // a real z pass is either the packed Nz/2-point kernel or the Bluestein kernel's real modes: never
-        // the plain complex chain (Nz == 2 would otherwise pick it and launch Bluestein without its tables)
-        const bool zreal_generic = !yzx && !c2c && !zr_native;
-        const bool zok = zreal_generic ? axis_plan_bluestein(p->prec, Nz, az, tl) : axis_plan(p->prec, zlen, az, mixed, tl);
-        if (!zok || !yok || !axis_plan(p->prec, Nx, axx, mixed, tl))
-            return fail(ERR_UNSUPPORTED, "unsupported axis length (every length from 2 to 2^23 has a plan; beyond that only lengths N1*N2 <= 2^24 whose "
-                                         "factors are each a power of two up to 8192 or any length up to 4096)");
-        // an axis outside the power-of-two kernels of this library runs kernels of libdfft_amd_any.so (any_loader.hip): no fallback
-        for (const Axis *a : {&az, &ay, &axx}) {
-            std::string why;
-            if ((a->bluestein || !is_pow2(a->N)) && !any_available(&why))
-                return fail(ERR_UNSUPPORTED, "an axis of " + std::to_string(a->N) + " points needs the kernels of libdfft_amd_any.so (every length that is "
-                                             "not a power of two up to 8192): " + why);
-        }
-        for (auto &a : p->ax) axis_free(a);
-        p->ax[0] = az; p->ax[1] = ay; p->ax[2] = axx;
-        p->zreal_native = zr_native;
-        p->yreal_native = yr_native;
-    }
+    TRY(plan_axes(p, Nx, Ny, Nz, c2c != 0, yzx));
     p->Nx = Nx; p->Ny = Ny; p->Nz = Nz; p->c2c = c2c != 0;
     p->Nzc = (c2c || yzx) ? Nz : Nz / 2 + 1;
     p->Nyc = (yzx && !c2c) ? Ny / 2 + 1 : Ny;      // Hermitian axis y (mpicufft_slab_y_then_zx.cpp:96-104)
@@ -1073,29 +820,7 @@ int dfft_init(dfft_plan *p, size_t Nx, size_t Ny, size_t Nz, int P1, int P2, int
     if (p->opt.spectral && (zyx || yzx)) return fail(ERR_UNSUPPORTED, "spectral_layout: pencil and default slab plans only (not the Z_Then_YX / Y_Then_ZX sequences)");
     if (p->opt.spectral && p->opt.spectral != 1) return fail(ERR_ARG, "spectral_layout: 0 = the reference's [Nx][yo][zs], 1 = x-contiguous [yo][zs][Nx]");
     if (p->opt.spectral_op) {
-        if ((zyx || yzx) && p->opt.spectral_op == 2)
-            return fail(ERR_UNSUPPORTED, "spectral_op: no fused chain for the Z_Then_YX / Y_Then_ZX sequences, whatever the x length (" + std::to_string(Nx) +
-                                         " points here): pencil and default slab plans only");
-        if (zyx || yzx) return fail(ERR_UNSUPPORTED, "spectral_op: pencil and default slab plans only (not the Z_Then_YX / Y_Then_ZX sequences)");
-        if (p->opt.spectral_op != 1 && p->opt.spectral_op != 2) return fail(ERR_ARG, "spectral_op: 0, 1 or 2");
-        // the fused x pass has the default configuration of the powers of two 2 .. 2048 (csrc/spectral_*.hip) and, with value 2, the
-        // mixed-radix lengths of csrc/spectral_mixed.inc (kernels of libdfft_amd_any.so); no unfused fallback
-        const Axis &ax = p->ax[2];
-        if (ax.bluestein || !is_pow2(Nx) || !(p->prec == DFFT_F64 ? spectral_supported_f64((int)Nx) : spectral_supported_f32((int)Nx))) {
-            if (p->opt.spectral_op == 1)
-                return fail(ERR_UNSUPPORTED, "spectral_op: an x length of " + std::to_string(Nx) + " points has no fused forward-multiply-inverse kernel "
-                                             "(powers of two from 2 to 2048 on a native chain)");
-            const std::string has = " (spectral_op = 2: powers of two from 2 to 2048 and the mixed-radix lengths 2^a 3^b 5^c 7^d up to 2000 that "
-                                    "dfft_spectral_op_supported reports, on a native chain)";
-            if (ax.bluestein)
-                return fail(ERR_UNSUPPORTED, "spectral_op: an x length of " + std::to_string(Nx) + " points runs the Bluestein / two-level kernel in this plan, "
-                                             "which has no fused forward-multiply-inverse form" + has);
-            std::string why;
-            if (!is_pow2(Nx) && !any_spectral_mixed_available(&why))
-                return fail(ERR_UNSUPPORTED, "spectral_op: the fused kernel of an x length of " + std::to_string(Nx) + " points is one of libdfft_amd_any.so: " + why);
-            if (is_pow2(Nx) || !(p->prec == DFFT_F64 ? spectral_mixed_supported_f64((int)Nx) : spectral_mixed_supported_f32((int)Nx)))
-                return fail(ERR_UNSUPPORTED, "spectral_op: an x length of " + std::to_string(Nx) + " points has no fused forward-multiply-inverse kernel" + has);
-        }
+        TRY(admit_spectral_op(p, zyx || yzx));
         p->worksize_d += p->domainsize;      // the slice that stands in for `out` (forward half) and `in` (inverse half)
     }
     // (one rank: the inverse of an x-contiguous spectrum cannot be the forward launches with conjugation -- their input is the natural grid)
@@ -1110,66 +835,13 @@ int dfft_init(dfft_plan *p, size_t Nx, size_t Ny, size_t Nz, int P1, int P2, int
         // largest launch (tiles x TL lines x N points)
         size_t lvb = 0;
         for (const Group &g : p->pl.groups)
-            for (const Launch &L : g.L) {
-                const Axis &a = p->ax[g.axis];
-                if (a.two) lvb = std::max(lvb, two_level_bytes(L.args, p->TL, a.N, p->esz));
-                if (a.longb) lvb = std::max(lvb, long_bytes(L.args, p->TL, a.M, p->esz));
-            }
+            for (const Launch &L : g.L) lvb = std::max(lvb, axis_scratch_bytes(p->prec, p->ax[g.axis], L.args, p->TL));
         p->worksize_d = (p->worksize_d + 255) & ~(size_t)255;
         p->lv_off = p->worksize_d;
         p->lv_bytes = (lvb + 255) & ~(size_t)255;
         p->worksize_d += p->lv_bytes;
     }
-    // kernel configuration per pass, by role (PassRole); lengths without a configuration for a role use the default
-    {
-        PassInfo vi;
-        auto has64 = [&](const Axis &a, int role) { return !a.bluestein && pass_info_f64((int)a.N, role, &vi); };
-        auto has32 = [&](const Axis &a, int role) { return !a.bluestein && pass_info_f32((int)a.N, role, &vi); };
-        for (int k = 0; k < 3; k++) p->vfwd[k] = p->vinv[k] = ROLE_DEFAULT;
-        if (p->prec == DFFT_F64) {
-            // the multi-rank inverse x pass reads the point-major API layout: 16 lines x 32 points (256-byte runs) -- where the rows
-            // are whole tiles.  On the 513-wide rows of an R2C plan the 256-byte runs straddle three cache lines and the one
-            // workgroup per CU re-reads 17 % of them (profiles/r3_pmc_traffic_f64_r2c.json): the default configuration (8 lines,
-            // two workgroups per CU) is 15 % faster there, 3.66 vs 4.26 ms at 1024^3 (profiles/r3_strided_read_odd_pitch.txt)
-            const size_t zs_local = p->zs.empty() ? p->Nzc : p->zs[p->zyx ? (size_t)p->rank % p->zs.size() : (size_t)p->pj % p->zs.size()];
-            if (has64(p->ax[2], ROLE_STRIDED_READ) && zs_local % (size_t)p->TL == 0) p->vinv[2] = ROLE_STRIDED_READ;
-            // ... and without a second exchange (P1 = 1) its persistent form with stores and loads fused (8.27 -> 7.64 ms at 1024^3,
-            // profiles/r4_persist3.txt); launches that do not have its pair of address forms run ROLE_STRIDED_READ by themselves
-            if (p->vinv[2] == ROLE_STRIDED_READ && p->P1 == 1 && has64(p->ax[2], ROLE_STRIDED_READ_FUSED)) p->vinv[2] = ROLE_STRIDED_READ_FUSED;
-            // complex z passes have natural lines on one side and long-run stores
-            const int zrole = has64(p->ax[0], ROLE_LINES) ? ROLE_LINES : has64(p->ax[0], ROLE_STREAM) ? ROLE_STREAM : ROLE_DEFAULT;
-            if (p->c2c) p->vfwd[0] = p->vinv[0] = zrole;
-            // the inverse y pass stores tiled-transpose chunks (1 KiB runs)
-            if (has64(p->ax[1], ROLE_STREAM)) p->vinv[1] = ROLE_STREAM;
-            if (p->opt.spectral) {      // x passes with natural lines on one side, like the complex z passes
-                const int xrole = has64(p->ax[2], ROLE_LINES) ? ROLE_LINES : has64(p->ax[2], ROLE_STREAM) ? ROLE_STREAM : ROLE_DEFAULT;
-                p->vfwd[2] = p->vinv[2] = xrole;
-            }
-        } else {
-            if (p->c2c && has32(p->ax[0], ROLE_NATURAL_LOAD)) p->vfwd[0] = ROLE_NATURAL_LOAD;
-            if (p->c2c && has32(p->ax[0], ROLE_NATURAL_STORE)) p->vinv[0] = ROLE_NATURAL_STORE;
-            for (int ax = 1; ax <= 2; ax++)
-                if (has32(p->ax[ax], ROLE_TILED)) p->vfwd[ax] = p->vinv[ax] = ROLE_TILED;
-            // the inverse y pass of a multi-rank plan stores transposed tiles: whole-line stores (ROLE_TRANSPOSED_STORE) where the length
-            // has such a configuration (2048 points: 4.80 -> 3.63 ms on rank 0 of 2 x 4 at 2048^3)
-            // (a single rank's complex inverse runs the forward launches: there vinv is not used)
-            if (has32(p->ax[1], ROLE_TRANSPOSED_STORE)) p->vinv[1] = ROLE_TRANSPOSED_STORE;
-            // 2048 points and more on a multi-rank plan: the forward y pass and the inverse x pass (the strided read of the API layout)
-            // run the streaming sibling of the tiled configuration -- what dfft_tune_variants picked on every 2048^3 plan measured
-            // (rank 0 of 2 x 4: y 4.93 -> 3.78 ms, x^-1 5.36 -> 4.46; of 8 x 1 the same two; profiles/r5_tuner_choices.txt).  The
-            // forward x pass and the inverse y pass lose with it (round 3), shorter lines were not measured: they keep their rule.
-            if (p->nranks > 1 && p->ax[1].N >= 2048 && has32(p->ax[1], ROLE_TILED_STREAM)) p->vfwd[1] = ROLE_TILED_STREAM;
-            if (p->nranks > 1 && p->ax[2].N >= 2048 && has32(p->ax[2], ROLE_TILED_STREAM)) p->vinv[2] = ROLE_TILED_STREAM;
-            if (p->opt.spectral) {      // x-contiguous spectrum: the forward x pass stores natural lines like the inverse z pass
-                if (has32(p->ax[2], ROLE_NATURAL_STORE)) p->vfwd[2] = ROLE_NATURAL_STORE;
-                // ... and its inverse loads them: point fastest for the first pass only, the same-tile stores stay line fastest
-                if (has32(p->ax[2], ROLE_NATURAL_LOAD_TILED_STORE)) p->vinv[2] = ROLE_NATURAL_LOAD_TILED_STORE;
-            }
-            // (The inverse y pass stores transposed tiles, which a line-fastest fp32 wave -- 16 lines x 4 points -- writes in 32-byte
-            // pieces.  A point-fastest store mapping, PassCfg::MAP = 2, writes whole lines and was measured: 1024 points 4.42 vs 4.30 ms,
-            // 2048 points 10.55 vs 10.35, no better -- L2 merges the pieces; profiles/r3_f32_inverse_y_point_fastest_store.txt.)
-        }
-    }
+    choose_pass_roles(p);
     for (int k = 0; k < 6; k++) {      // per-pass overrides (dfft_set_option): fz fy fx ix iy iz
         const int d = p->opt.order[k];
         if (std::vector<Launch> *v = d >= 0 ? pass_launches(p, k) : nullptr)
@@ -1381,9 +1053,8 @@ int dfft_spectral_op_supported(int precision, size_t Nx, int option_value)
 {
     if ((precision != DFFT_F64 && precision != DFFT_F32) || (option_value != 1 && option_value != 2)) return 0;
     Axis ax;
-    if (!axis_plan(precision, Nx, ax) || ax.bluestein) return 0;      // the x axis of dfft_init with default options
-    if (is_pow2(Nx)) return (precision == DFFT_F64 ? spectral_supported_f64((int)Nx) : spectral_supported_f32((int)Nx)) ? 1 : 0;
-    return option_value == 2 && (precision == DFFT_F64 ? spectral_mixed_supported_f64((int)Nx) : spectral_mixed_supported_f32((int)Nx)) ? 1 : 0;
+    if (!axis_plan(precision, Nx, ax)) return 0;      // the x axis of dfft_init with default options
+    return spectral_kernel_for(precision, ax, option_value, nullptr) != SPECTRAL_NONE ? 1 : 0;
 }
 
 int dfft_exec_spectral_op(dfft_plan *p, void *out, const void *in, const dfft_spectral_op *op)
@@ -1681,9 +1352,8 @@ int dfft_fft1d_batched_ex(int precision, size_t N, size_t batch, void *out, cons
         return r == 0 ? 0 : fail(r == -1 ? ERR_UNSUPPORTED : r, "shuffle pass launch failed");
     }
 #endif
-    PassInfo pi;
-    const bool has = !ax.bluestein && variant ? (precision == DFFT_F64 ? pass_info_f64((int)ax.M, variant, &pi) : pass_info_f32((int)ax.M, variant, &pi)) : false;
-    if (!has) {
+    PassInfo pi;      // the tile lines of the configuration that runs: the variant's, else the default one's
+    if (!(variant && has_variant(precision, ax, variant, &pi))) {
         variant = 0;
         if (!pass_info(precision, ax.two || ax.longb ? 2 : (int)ax.M, &pi)) return fail(ERR_UNSUPPORTED, "unsupported line length");      // (two levels: any configuration gives TL)
     }
@@ -1692,21 +1362,13 @@ int dfft_fft1d_batched_ex(int precision, size_t N, size_t batch, void *out, cons
     A.in = in; A.out = out; A.tw = ax.tw; A.debug = debug;
     A.na = 1; A.LB = (uint32_t)batch; A.nb = ((uint32_t)batch + pi.TL - 1) / pi.TL; A.ntiles = A.nb;
     A.load_kind = LOAD_LINES; A.store_kind = STORE_LINES; A.swap = direction == DFFT_INVERSE;
-    if (!ax.bluestein) return launch_pass(precision, (int)N, variant, A, (hipStream_t)hip_stream);
-    if (ax.two || ax.longb) {
-        const size_t need = ax.longb ? long_bytes(A, pi.TL, ax.M, precision == DFFT_F64 ? 16 : 8) : two_level_bytes(A, pi.TL, N, precision == DFFT_F64 ? 16 : 8);
-        if (need > lvw_bytes) {
-            if (lvw) { (void)hipFree(lvw); lvw = nullptr; lvw_bytes = 0; }      // (hipFree waits for the launches that still use it)
-            HIP_TRY(hipMalloc(&lvw, need));
-            lvw_bytes = need;
-        }
-        if (ax.longb) return launch_long_bluestein(precision, ax, A, 0, N, lvw, pi.TL, (hipStream_t)hip_stream);
-        return launch_two_level(precision, ax, A, 0, N, lvw, pi.TL, (hipStream_t)hip_stream);
+    const size_t need = axis_scratch_bytes(precision, ax, A, pi.TL);
+    if (need > lvw_bytes) {
+        if (lvw) { (void)hipFree(lvw); lvw = nullptr; lvw_bytes = 0; }      // (hipFree waits for the launches that still use it)
+        HIP_TRY(hipMalloc(&lvw, need));
+        lvw_bytes = need;
     }
-    A.NK = (uint32_t)N;
-    int r = launch_generic(precision, ax, A, (hipStream_t)hip_stream);
-    if (r != 0) return fail(r == -1 ? ERR_UNSUPPORTED : r, "Bluestein launch failed");
-    return 0;
+    return launch_axis(precision, ax, A, variant, 0, N, lvw, lvw_bytes, pi.TL, (hipStream_t)hip_stream);
 }
 int dfft_fft1d_batched(int precision, size_t N, size_t batch, void *out, const void *in, int direction,
                        void *hip_stream)

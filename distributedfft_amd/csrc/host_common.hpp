@@ -1,4 +1,4 @@
-// host_common.hpp -- error plumbing shared by the host translation units of libdfft_amd.so (dfft.hip, alloc.hip): every failure
+// host_common.hpp -- error plumbing shared by the host translation units of libdfft_amd.so (dfft.hip, axis.hip, alloc.hip): every failure
 // sets the thread's message (dfft_last_error) and returns a code, nothing throws.
 #pragma once
 #include <hip/hip_runtime.h>

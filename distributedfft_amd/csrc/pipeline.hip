@@ -1,6 +1,6 @@
 // pipeline.hip -- the pass descriptors and exchange tables of every decomposition (the layout algebra of DESIGN.md section 2):
 // which lines a pass transforms, how its load and store sides address the buffers, which bytes go to which peer, per pipeline chunk.
-// Host code only; its own translation unit since round 6 (csrc/dfft.hip keeps axis plans, execution chains, tuners and the C ABI).
+// Host code only; its own translation unit since round 6 (csrc/dfft.hip keeps dfft_init, the execution chains and the C ABI; axis plans: csrc/axis.hip).
 #include <string.h>
 
 #include <algorithm>

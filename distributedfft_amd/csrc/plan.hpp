@@ -1,5 +1,6 @@
-// plan.hpp -- the plan object of libdfft_amd.so and what its host translation units share: dfft.hip (axis plans, execution chains,
-// tuners, C ABI) and pipeline.hip (the pass descriptors and exchange tables of every decomposition).
+// plan.hpp -- the plan object of libdfft_amd.so and what its host translation units share: dfft.hip (dfft_init, execution chains,
+// C ABI), axis.hip (axis plans and their launches: axis.hpp), pipeline.hip (the pass descriptors and exchange tables of every
+// decomposition) and tune.hip (the tuners).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -210,6 +211,7 @@ struct dfft_plan {
     int last_dir = -1;
     std::vector<dfft_trace_op> trace_log[3];   // option trace: what the last forward / inverse / spectral-operator exec issued
     dfft_spectral_op op{};                     // the multiplier of the spectral-operator exec being enqueued
+    int spectral_kernel = 0;                   // option spectral_op: the fused x kernel dfft_init found (dfft::SpectralKernel, axis.hpp)
     // hipGraph replay of single-rank execs (launch-bound small grids): one instantiated graph per (operation, in, out)
     struct GraphEntry { int kind; const void *in; void *out; int uses; hipGraphExec_t exec; };
     std::vector<GraphEntry> graphs;

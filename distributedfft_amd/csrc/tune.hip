@@ -10,8 +10,8 @@
 #include <vector>
 
 #include "alloc.hpp"
+#include "axis.hpp"
 #include "host_common.hpp"
-#include "plan.hpp"
 
 using namespace dfft;
 
@@ -124,11 +124,7 @@ static int tune_variants(dfft_plan *p, const void *in, void *o, void *b, float &
     note(total);
     float cur[6];
     for (int k = 0; k < 6; k++) cur[k] = t[k];
-    auto exists = [&](int k, int v) {
-        PassInfo pi;
-        const Axis &a = p->ax[axis_of(k)];
-        return !a.bluestein && (p->prec == DFFT_F64 ? pass_info_f64((int)a.N, v, &pi) : pass_info_f32((int)a.N, v, &pi));
-    };
+    auto exists = [&](int k, int v) { return has_variant(p->prec, p->ax[axis_of(k)], v); };
     auto tunable = [&](int k) { return usable(k) && p->opt.variant[k] < 0 && !p->ax[axis_of(k)].bluestein && !(p->c2c == false && axis_of(k) == 0); };
     // only the role variants that the parity suite runs on every pass and address form (tests/test_gpu_variants.py); an A/B build
     // (-DDFFT_EXPERIMENTS) carries further configuration numbers that are measured by hand, never picked here
