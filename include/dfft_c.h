@@ -235,19 +235,32 @@ int dfft_set_stream(dfft_plan *plan, void *hip_stream);
 /* execR2C(void *out, const void *in)   include/mpicufft.hpp:63; mpicufft_pencil_opt1.cpp:1422-1519.
  * in: device, real [xs][ys][Nz], not modified.  out: device, >= dfft_domain_size() bytes;
  * holds [Nx][yo][zs] complex on return.  Blocking (returns after the stream is drained), like
- * the reference's trailing cudaDeviceSynchronize. */
+ * the reference's trailing cudaDeviceSynchronize.
+ * Footprint of every exec entry point (tests/test_gpu_footprint.py holds each of them to it on guarded buffers): an exec reads and
+ * writes inside `in`, `out` and the dfft_work_size_device() bytes of the work area and nowhere else, and its result does not depend
+ * on what `out` or the work area held before.  Alignment: every device pointer (in, out, the work area, multiplier arrays and
+ * tables) must be aligned to 16 bytes, the size of an fp64 complex point.  Beyond that alignment is a matter of speed only: tile
+ * windows and their cache-line shifts are computed relative to the buffer's base, and they fill whole 128-byte lines when the base
+ * is 128-byte aligned, as every hipMalloc result and the 256-byte-aligned slices of the library's own work area are.  (The tests run
+ * buffers at 2 MiB alignment and, for the ragged and odd-pitch cases, again 256 bytes off it.) */
 int dfft_exec_r2c(dfft_plan *plan, void *out, const void *in);
 /* execC2R(void *out, const void *in)   include/mpicufft_pencil.hpp:106-111; :1522-1600.
- * `in` is DESTROYED (used as scratch, as in the reference :1534,1544,1563). */
+ * `in` is DESTROYED (used as scratch, as in the reference :1534,1544,1563): it must hold dfft_domain_size() bytes, like the `out`
+ * of the forward transform that filled it.  out: the input block [xs][ys][Nz], real; exactly its size is written, no more is needed. */
 int dfft_exec_c2r(dfft_plan *plan, void *out, void *in);
 /* new: complex-to-complex, same layouts with Nz_out = Nz.  Forward: in [xs][ys][Nz] -> out
- * [Nx][yo][zs].  Inverse: in [Nx][yo][zs] (destroyed) -> out [xs][ys][Nz]. */
+ * [Nx][yo][zs].  Inverse: in [Nx][yo][zs] (destroyed) -> out [xs][ys][Nz].
+ * Forward: `in` is not modified (the pointer is not const because the inverse shares the entry point); out >= dfft_domain_size()
+ * bytes.  Inverse: `in` must hold dfft_domain_size() bytes (scratch); out: the input block's size, xs * ys * Nz complex, is enough. */
 int dfft_exec_c2c(dfft_plan *plan, void *out, void *in, int direction);
 /* partial transforms: execR2C(out, in, d) / execC2R(out, in, d) of MPIcuFFT_Pencil
  * (include/mpicufft_pencil.hpp:101-111, src/pencil/mpicufft_pencil.cpp:1644-1839).  Works for
  * R2C and C2C plans alike (the plan decides).  d = 3: the full transform.  d = 1: z axis only,
  * stage layout [xs][ys][Nzc] (natural, z contiguous).  d = 2: z then y, stage layout
- * [xs][Ny][zs].  The inverse direction takes those layouts as input and returns [xs][ys][Nz]. */
+ * [xs][Ny][zs].  The inverse direction takes those layouts as input and returns [xs][ys][Nz].
+ * Forward (every d): `in` is not modified; the stage layouts are never larger than dfft_domain_size() bytes, which is what `out`
+ * must hold.  Inverse, d = 1, 2: `in` holds the stage layout and may be used as scratch like that of the full inverse; out: the
+ * input block's size (xs * ys * Nz real resp. complex entries) is enough. */
 int dfft_exec_dim(dfft_plan *plan, void *out, void *in, int direction, int d);
 /* non-blocking variants: enqueue only (caller synchronises the stream) */
 int dfft_enqueue_c2c(dfft_plan *plan, void *out, void *in, int direction);

@@ -48,23 +48,39 @@ def test_fft1d_batched_vs_oracle(N, prec):
                           label=f"fft1d N={N} dir={direction} mean={x.real.mean():.0f}" if N in (8, 1024, 8192) else None)
 
 
-def run_single(shape, prec, seed=5, center=False):
+def run_single(shape, prec, seed=5, center=False, arena=None):
+    """arena (tests/guarded.py): every buffer and a caller-owned work area come from it, refilled before either exec, and the guards and
+    the input are checked after either exec; a second call with the same arena runs the plan and the buffers of the first"""
     g = orc.fill_block(shape, (0, 0, 0), shape, 2, seed=seed)
     if center:
         g = g - CENTER * (1 + 1j)
     g = g.astype(NPDT[prec])
-    plan = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), precision=prec)
-    plan.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(1, 1), True, c2c=True)
     esz = 16 if prec == "double" else 8
-    d_in = torch.from_numpy(g).cuda()
-    d_out = torch.zeros(plan.getDomainSize() // esz, dtype=CDT[prec], device="cuda")
+
+    def setup():
+        plan = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), precision=prec)
+        plan.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(1, 1), arena is None, c2c=True)
+        if arena is not None:
+            return (plan,) + arena.plan_buffers(plan, g, CDT[prec])
+        return plan, torch.from_numpy(g).cuda(), torch.zeros(plan.getDomainSize() // esz, dtype=CDT[prec], device="cuda"), None
+
+    plan, d_in, d_out, d_back = setup() if arena is None else arena.once("run_single", setup)
+    if arena is not None:
+        arena.refill()
     torch.cuda.synchronize()
     plan.execC2C(d_out, d_in, dfft.FORWARD)
     got = d_out[:g.size].cpu().numpy().reshape(shape)
     assert np.array_equal(d_in.cpu().numpy(), g), "forward must not modify its input"
-    d_back = torch.zeros_like(d_in)
+    if arena is None:
+        d_back = torch.zeros_like(d_in)
+    else:
+        arena.check_guards(f"run_single {shape} {prec} forward")
+        arena.check_inputs(f"run_single {shape} {prec} forward")
+        arena.refill(keep=[d_out])
     torch.cuda.synchronize()      # the fill runs on torch's stream, the plan on its own
     plan.execC2C(d_back, d_out, dfft.INVERSE)
+    if arena is not None:
+        arena.check_guards(f"run_single {shape} {prec} inverse")
     return g, got, d_back.cpu().numpy()
 
 
@@ -89,40 +105,59 @@ def test_golden_fixture_single_rank():
     assert rel(got, d["c2c_8x8x8"]) < 1e-11
 
 
-def run_distributed(shape, P1, P2, prec, seed=7, chunks=None, options=None, comm_options=None, center=False):
+def run_distributed(shape, P1, P2, prec, seed=7, chunks=None, options=None, comm_options=None, center=False, arena=None):
     """P1*P2 virtual ranks on one GPU (one host thread per rank, like MPI ranks sharing a
-    device: tests/src/pencil/random_dist_3D.cu:175-177)."""
+    device: tests/src/pencil/random_dist_3D.cu:175-177).  arena: as in run_single."""
     P = P1 * P2
-    world = dfft.Comm.local(P)
-    for k, v in (comm_options or {}).items():
-        world.setOption(k, v)
     esz = 16 if prec == "double" else 8
-    plans, ins, outs, backs = [], [], [], []
-    for r in range(P):
-        pl = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), world, precision=prec, rank=r)
-        if chunks is not None:
-            pl.setPipelineChunks(chunks)
-        for k, v in (options or {}).items():
-            pl.setOption(k, v)
-        pl.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(P1, P2), True, c2c=True)
-        size, start = pl.getInSize(), pl.getInStart()
-        blk = orc.fill_block(shape, start, size, 2, seed=seed)
-        if center:
-            blk = blk - CENTER * (1 + 1j)
-        blk = blk.astype(NPDT[prec])
-        plans.append(pl)
-        ins.append(torch.from_numpy(blk).cuda())
-        outs.append(torch.zeros(pl.getDomainSize() // esz, dtype=CDT[prec], device="cuda"))
-        backs.append(torch.zeros_like(ins[-1]))
+
+    def setup():
+        world = dfft.Comm.local(P)
+        for k, v in (comm_options or {}).items():
+            world.setOption(k, v)
+        plans, ins, outs, backs = [], [], [], []
+        for r in range(P):
+            pl = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), world, precision=prec, rank=r)
+            if chunks is not None:
+                pl.setPipelineChunks(chunks)
+            for k, v in (options or {}).items():
+                pl.setOption(k, v)
+            pl.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(P1, P2), arena is None, c2c=True)
+            size, start = pl.getInSize(), pl.getInStart()
+            blk = orc.fill_block(shape, start, size, 2, seed=seed)
+            if center:
+                blk = blk - CENTER * (1 + 1j)
+            blk = blk.astype(NPDT[prec])
+            plans.append(pl)
+            if arena is not None:
+                for lst, t in zip((ins, outs, backs), arena.plan_buffers(pl, blk, CDT[prec], r)):
+                    lst.append(t)
+                continue
+            ins.append(torch.from_numpy(blk).cuda())
+            outs.append(torch.zeros(pl.getDomainSize() // esz, dtype=CDT[prec], device="cuda"))
+            backs.append(torch.zeros_like(ins[-1]))
+        return plans, ins, outs, backs
+
+    plans, ins, outs, backs = setup() if arena is None else arena.once("run_distributed", setup)
+    what = f"run_distributed {shape} {P1}x{P2} {prec} {options or ''}"
+    if arena is not None:
+        arena.refill()
     torch.cuda.synchronize()
     with ThreadPoolExecutor(P) as ex:
         list(ex.map(lambda r: plans[r].execC2C(outs[r], ins[r], dfft.FORWARD), range(P)))
+    if arena is not None:
+        arena.check_guards(what + " forward")
+        arena.check_inputs(what + " forward")
     spec = []
     for r in range(P):      # (Nx, yo, zs) whatever the plan's spectral layout (option spectral_layout)
         spec.append(plans[r].spectrumView(outs[r]).contiguous().cpu().numpy())
+    if arena is not None:
+        arena.refill(keep=outs)
     with ThreadPoolExecutor(P) as ex:
         list(ex.map(lambda r: plans[r].execC2C(backs[r], outs[r], dfft.INVERSE), range(P)))
     torch.cuda.synchronize()
+    if arena is not None:
+        arena.check_guards(what + " inverse")
     return plans, [t.cpu().numpy() for t in ins], spec, [t.cpu().numpy() for t in backs]
 
 
@@ -163,30 +198,48 @@ RDT = {"double": torch.float64, "float": torch.float32}
 NPR = {"double": np.float64, "float": np.float32}
 
 
-def run_distributed_real(shape, P1, P2, prec, field=None, seed=13, modify=None, options=None, comm_options=None):
+def run_distributed_real(shape, P1, P2, prec, field=None, seed=13, modify=None, options=None, comm_options=None, chunks=None, arena=None):
+    """arena: as in run_single"""
     P = P1 * P2
-    world = dfft.Comm.local(P) if P > 1 else None
-    for k, v in (comm_options or {}).items():
-        world.setOption(k, v)
     esz = 16 if prec == "double" else 8
-    plans, ins, outs, backs = [], [], [], []
-    for r in range(P):
-        pl = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), world, precision=prec, rank=r)
-        for k, v in (options or {}).items():
-            pl.setOption(k, v)
-        pl.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(P1, P2), True)      # R2C plan
-        size, start = pl.getInSize(), pl.getInStart()
-        if field is None:
-            blk = orc.fill_block(shape, start, size, 1, seed=seed)
-        else:
-            blk = np.ascontiguousarray(field[start[0]:start[0] + size[0], start[1]:start[1] + size[1], :])
-        plans.append(pl)
-        ins.append(torch.from_numpy(blk.astype(NPR[prec])).cuda())
-        outs.append(torch.zeros(pl.getDomainSize() // esz, dtype=CDT[prec], device="cuda"))
-        backs.append(torch.zeros_like(ins[-1]))
+
+    def setup():
+        world = dfft.Comm.local(P) if P > 1 else None
+        for k, v in (comm_options or {}).items():
+            world.setOption(k, v)
+        plans, ins, outs, backs = [], [], [], []
+        for r in range(P):
+            pl = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), world, precision=prec, rank=r)
+            if chunks is not None:
+                pl.setPipelineChunks(chunks)
+            for k, v in (options or {}).items():
+                pl.setOption(k, v)
+            pl.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(P1, P2), arena is None)      # R2C plan
+            size, start = pl.getInSize(), pl.getInStart()
+            if field is None:
+                blk = orc.fill_block(shape, start, size, 1, seed=seed)
+            else:
+                blk = np.ascontiguousarray(field[start[0]:start[0] + size[0], start[1]:start[1] + size[1], :])
+            plans.append(pl)
+            if arena is not None:
+                for lst, t in zip((ins, outs, backs), arena.plan_buffers(pl, blk.astype(NPR[prec]), CDT[prec], r)):
+                    lst.append(t)
+                continue
+            ins.append(torch.from_numpy(blk.astype(NPR[prec])).cuda())
+            outs.append(torch.zeros(pl.getDomainSize() // esz, dtype=CDT[prec], device="cuda"))
+            backs.append(torch.zeros_like(ins[-1]))
+        return plans, ins, outs, backs
+
+    plans, ins, outs, backs = setup() if arena is None else arena.once("run_distributed_real", setup)
+    what = f"run_distributed_real {shape} {P1}x{P2} {prec} {options or ''}"
+    if arena is not None:
+        arena.refill()
     torch.cuda.synchronize()
     with ThreadPoolExecutor(P) as ex:
         list(ex.map(lambda r: plans[r].execR2C(outs[r], ins[r]), range(P)))
+    if arena is not None:
+        arena.check_guards(what + " forward")
+        arena.check_inputs(what + " forward")
     spec = []
     for r in range(P):      # (Nx, yo, zs) whatever the plan's spectral layout (option spectral_layout)
         spec.append(plans[r].spectrumView(outs[r]).contiguous().cpu().numpy())
@@ -196,10 +249,14 @@ def run_distributed_real(shape, P1, P2, prec, field=None, seed=13, modify=None, 
             blk = np.ascontiguousarray(spec[r].astype(np.complex128))
             modify(blk, s, o)
             plans[r].spectrumView(outs[r]).copy_(torch.from_numpy(blk.astype(NPDT[prec])).cuda())
+    if arena is not None:
+        arena.refill(keep=outs)
     torch.cuda.synchronize()
     with ThreadPoolExecutor(P) as ex:
         list(ex.map(lambda r: plans[r].execC2R(backs[r], outs[r]), range(P)))
     torch.cuda.synchronize()
+    if arena is not None:
+        arena.check_guards(what + " inverse")
     return plans, [t.cpu().numpy() for t in ins], spec, [t.cpu().numpy() for t in backs]
 
 
@@ -313,11 +370,11 @@ def test_pipelined_exchange_chunks(shape, P1, P2, chunks):
 # partial transforms: MPIcuFFT_Pencil::execR2C/execC2R(out, in, d), d = 1, 2
 # (reference tests random_dist_1D.cu:180-451, random_dist_2D.cu:181-455)
 # ------------------------------------------------------------------------------------------
-def run_partial(shape, P1, P2, d, c2c, two_level=0, prec="double", center=False, seed=31):
+def run_partial(shape, P1, P2, d, c2c, two_level=0, prec="double", center=False, seed=31, arena=None):
     """execC2C / execR2C(out, in, d) and back on P1*P2 virtual ranks: (plans, global input, per-rank (got, want) blocks of the partial
-    spectrum, the whole partial spectrum, inputs, round trips); the reference is numpy's transform along z (d = 1), then y (d = 2)"""
+    spectrum, the whole partial spectrum, inputs, round trips); the reference is numpy's transform along z (d = 1), then y (d = 2).
+    arena: as in run_single (the forward partial transforms only read `in`: include/dfft_c.h)"""
     P = P1 * P2
-    world = dfft.Comm.local(P) if P > 1 else None
     Nx, Ny, Nz = shape
     Nzc = Nz if c2c else Nz // 2 + 1
     esz = 16 if prec == "double" else 8
@@ -330,17 +387,30 @@ def run_partial(shape, P1, P2, d, c2c, two_level=0, prec="double", center=False,
     ref = np.fft.fft(g64, axis=2) if c2c else np.fft.rfft(g64, axis=2)
     if d == 2:
         ref = np.fft.fft(ref, axis=1)
-    plans, ins, outs, backs = [], [], [], []
-    for r in range(P):
-        pl = dfft.MPIcuFFT_Pencil(dfft.Configurations(), world, precision=prec, rank=r)
-        pl.setOption("two_level", two_level)
-        pl.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(P1, P2), True, c2c=c2c)
-        s, o = pl.getInSize(), pl.getInStart()
-        blk = np.ascontiguousarray(g[o[0]:o[0] + s[0], o[1]:o[1] + s[1], :])
-        plans.append(pl)
-        ins.append(torch.from_numpy(blk).cuda())
-        outs.append(torch.zeros(pl.getDomainSize() // esz, dtype=CDT[prec], device="cuda"))
-        backs.append(torch.zeros_like(ins[-1]))
+
+    def setup():
+        world = dfft.Comm.local(P) if P > 1 else None
+        plans, ins, outs, backs = [], [], [], []
+        for r in range(P):
+            pl = dfft.MPIcuFFT_Pencil(dfft.Configurations(), world, precision=prec, rank=r)
+            pl.setOption("two_level", two_level)
+            pl.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(P1, P2), arena is None, c2c=c2c)
+            s, o = pl.getInSize(), pl.getInStart()
+            blk = np.ascontiguousarray(g[o[0]:o[0] + s[0], o[1]:o[1] + s[1], :])
+            plans.append(pl)
+            if arena is not None:
+                for lst, t in zip((ins, outs, backs), arena.plan_buffers(pl, blk, CDT[prec], r)):
+                    lst.append(t)
+                continue
+            ins.append(torch.from_numpy(blk).cuda())
+            outs.append(torch.zeros(pl.getDomainSize() // esz, dtype=CDT[prec], device="cuda"))
+            backs.append(torch.zeros_like(ins[-1]))
+        return plans, ins, outs, backs
+
+    plans, ins, outs, backs = setup() if arena is None else arena.once("run_partial", setup)
+    what = f"run_partial {shape} {P1}x{P2} d={d} {'C2C' if c2c else 'R2C'} {prec}"
+    if arena is not None:
+        arena.refill()
     torch.cuda.synchronize()
 
     def fwd(r):
@@ -358,6 +428,9 @@ def run_partial(shape, P1, P2, d, c2c, two_level=0, prec="double", center=False,
     with ThreadPoolExecutor(P) as ex:
         list(ex.map(fwd, range(P)))
     torch.cuda.synchronize()
+    if arena is not None:
+        arena.check_guards(what + " forward")
+        arena.check_inputs(what + " forward")
     blocks = []
     for r, pl in enumerate(plans):
         isz, ist = pl.getInSize(), pl.getInStart()
@@ -369,9 +442,13 @@ def run_partial(shape, P1, P2, d, c2c, two_level=0, prec="double", center=False,
             shp = (isz[0], Ny, osz[2])
             want = ref[ist[0]:ist[0] + isz[0], :, ost[2]:ost[2] + osz[2]]
         blocks.append((outs[r][:int(np.prod(shp))].cpu().numpy().reshape(shp), want))
+    if arena is not None:
+        arena.refill(keep=outs)
     with ThreadPoolExecutor(P) as ex:
         list(ex.map(inv, range(P)))
     torch.cuda.synchronize()
+    if arena is not None:
+        arena.check_guards(what + " inverse")
     return plans, blocks, ref, [t.cpu().numpy() for t in ins], [t.cpu().numpy() for t in backs]
 
 

@@ -417,24 +417,40 @@ def test_c5_shaped_2048x2048x1024_fp32_pencil_2x4_every_point():
 # ------------------------------------------------------------------------------------------
 # single-rank pass order z, x, y, forced
 # ------------------------------------------------------------------------------------------
-def run_single_order(shape, prec, options, seed=5, center=False):
+def run_single_order(shape, prec, options, seed=5, center=False, arena=None):
+    """arena: as in test_gpu_parity.run_single"""
     g = orc.fill_block(shape, (0, 0, 0), shape, 2, seed=seed)
     if center:
         g = g - CENTER * (1 + 1j)
     g = g.astype(NPDT[prec])
-    plan = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), precision=prec)
-    for k, v in options.items():
-        plan.setOption(k, v)
-    plan.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(1, 1), True, c2c=True)
     esz = 16 if prec == "double" else 8
-    d_in = torch.from_numpy(g).cuda()
-    d_out = torch.zeros(plan.getDomainSize() // esz, dtype=CDT[prec], device="cuda")
+
+    def setup():
+        plan = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), precision=prec)
+        for k, v in options.items():
+            plan.setOption(k, v)
+        plan.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(1, 1), arena is None, c2c=True)
+        if arena is not None:
+            return (plan,) + arena.plan_buffers(plan, g, CDT[prec])
+        return plan, torch.from_numpy(g).cuda(), torch.zeros(plan.getDomainSize() // esz, dtype=CDT[prec], device="cuda"), None
+
+    plan, d_in, d_out, d_back = setup() if arena is None else arena.once("run_single_order", setup)
+    what = f"run_single_order {shape} {prec} {options}"
+    if arena is not None:
+        arena.refill()
     torch.cuda.synchronize()
     plan.execC2C(d_out, d_in, dfft.FORWARD)
     got = d_out[:g.size].cpu().numpy().reshape(shape)
-    d_back = torch.zeros_like(d_in)
+    if arena is None:
+        d_back = torch.zeros_like(d_in)
+    else:
+        arena.check_guards(what + " forward")
+        arena.check_inputs(what + " forward")
+        arena.refill(keep=[d_out])
     torch.cuda.synchronize()
     plan.execC2C(d_back, d_out, dfft.INVERSE)
+    if arena is not None:
+        arena.check_guards(what + " inverse")
     return g, got, d_back.cpu().numpy()
 
 

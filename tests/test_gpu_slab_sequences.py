@@ -24,36 +24,53 @@ NPC = {"double": np.complex128, "float": np.complex64}
 NPR = {"double": np.float64, "float": np.float32}
 
 
-def run(cls, shape, P, prec, c2c, chunks=None, field=None, modify=None, seed=21, options=None, center=False):
-    world = dfft.Comm.local(P) if P > 1 else None
+def run(cls, shape, P, prec, c2c, chunks=None, field=None, modify=None, seed=21, options=None, center=False, arena=None):
+    """arena (tests/guarded.py): every buffer and a caller-owned work area come from it, refilled before either exec, and the guards and
+    the inputs are checked after either exec; a second call with the same arena runs the plans and the buffers of the first"""
     esz = 16 if prec == "double" else 8
-    plans, ins, outs, backs, host_ins = [], [], [], [], []
-    for r in range(P):
-        pl = cls(dfft.Configurations(), world, precision=prec, rank=r)
-        if chunks is not None:
-            pl.setPipelineChunks(chunks)
-        for k, v in (options or {}).items():
-            pl.setOption(k, v)
-        pl.initFFT(dfft.GlobalSize(*shape), dfft.Slab_Partition(P), True, c2c=c2c)
-        size, start = pl.getInSize(), pl.getInStart()
-        assert tuple(size[1:]) == tuple(shape[1:]) and tuple(start[1:]) == (0, 0)
-        if field is not None:
-            blk = np.ascontiguousarray(field[start[0]:start[0] + size[0]]).astype(NPR[prec])
-        elif c2c:
-            blk = (orc.fill_block(shape, start, size, 2, seed=seed) - (CENTER * (1 + 1j) if center else 0.0)).astype(NPC[prec])
-        else:
-            blk = (orc.fill_block(shape, start, size, 1, seed=seed) - (CENTER if center else 0.0)).astype(NPR[prec])
-        plans.append(pl)
-        host_ins.append(blk.copy())
-        ins.append(torch.from_numpy(blk).cuda())
-        outs.append(torch.zeros(pl.getDomainSize() // esz, dtype=CDT[prec], device="cuda"))
-        backs.append(torch.zeros_like(ins[-1]))
+
+    def setup():
+        world = dfft.Comm.local(P) if P > 1 else None
+        plans, ins, outs, backs, host_ins = [], [], [], [], []
+        for r in range(P):
+            pl = cls(dfft.Configurations(), world, precision=prec, rank=r)
+            if chunks is not None:
+                pl.setPipelineChunks(chunks)
+            for k, v in (options or {}).items():
+                pl.setOption(k, v)
+            pl.initFFT(dfft.GlobalSize(*shape), dfft.Slab_Partition(P), arena is None, c2c=c2c)
+            size, start = pl.getInSize(), pl.getInStart()
+            assert tuple(size[1:]) == tuple(shape[1:]) and tuple(start[1:]) == (0, 0)
+            if field is not None:
+                blk = np.ascontiguousarray(field[start[0]:start[0] + size[0]]).astype(NPR[prec])
+            elif c2c:
+                blk = (orc.fill_block(shape, start, size, 2, seed=seed) - (CENTER * (1 + 1j) if center else 0.0)).astype(NPC[prec])
+            else:
+                blk = (orc.fill_block(shape, start, size, 1, seed=seed) - (CENTER if center else 0.0)).astype(NPR[prec])
+            plans.append(pl)
+            host_ins.append(blk.copy())
+            if arena is not None:
+                for lst, t in zip((ins, outs, backs), arena.plan_buffers(pl, blk, CDT[prec], r)):
+                    lst.append(t)
+                continue
+            ins.append(torch.from_numpy(blk).cuda())
+            outs.append(torch.zeros(pl.getDomainSize() // esz, dtype=CDT[prec], device="cuda"))
+            backs.append(torch.zeros_like(ins[-1]))
+        return plans, ins, outs, backs, host_ins
+
+    plans, ins, outs, backs, host_ins = setup() if arena is None else arena.once("slabs.run", setup)
+    what = f"slabs.run {cls.__name__} {shape} P={P} {'C2C' if c2c else 'R2C'} {prec}"
+    if arena is not None:
+        arena.refill()
     torch.cuda.synchronize()
     fwd = (lambda r: plans[r].execC2C(outs[r], ins[r], dfft.FORWARD)) if c2c else (lambda r: plans[r].execR2C(outs[r], ins[r]))
     inv = (lambda r: plans[r].execC2C(backs[r], outs[r], dfft.INVERSE)) if c2c else (lambda r: plans[r].execC2R(backs[r], outs[r]))
     with ThreadPoolExecutor(P) as ex:
         list(ex.map(fwd, range(P)))
     torch.cuda.synchronize()
+    if arena is not None:
+        arena.check_guards(what + " forward")
+        arena.check_inputs(what + " forward")
     spec = []
     for r in range(P):
         s = plans[r].getOutSize()
@@ -67,9 +84,13 @@ def run(cls, shape, P, prec, c2c, chunks=None, field=None, modify=None, seed=21,
     torch.cuda.synchronize()
     for r in range(P):
         assert np.array_equal(ins[r].cpu().numpy(), host_ins[r]), "forward must not modify its input"
+    if arena is not None:
+        arena.refill(keep=outs)
     with ThreadPoolExecutor(P) as ex:
         list(ex.map(inv, range(P)))
     torch.cuda.synchronize()
+    if arena is not None:
+        arena.check_guards(what + " inverse")
     return plans, [t.cpu().numpy() for t in ins], spec, [t.cpu().numpy() for t in backs]
 
 
@@ -166,31 +187,49 @@ def test_z_then_yx_errors_and_single_rank():
 # ------------------------------------------------------------------------------------------
 # Y_Then_ZX (src/slab/y_then_zx/): R2C along y, output [Nx][(Ny/2+1)/P][Nz], forward only
 # ------------------------------------------------------------------------------------------
-def run_yzx(shape, P, prec, c2c, chunks=None, seed=33, options=None, center=False):
-    world = dfft.Comm.local(P) if P > 1 else None
+def run_yzx(shape, P, prec, c2c, chunks=None, seed=33, options=None, center=False, arena=None):
+    """arena: as in run (forward only: `in`, `out` and the work area)"""
     esz = 16 if prec == "double" else 8
-    plans, ins, outs, host_ins = [], [], [], []
-    for r in range(P):
-        pl = dfft.MPIcuFFT_Slab_Y_Then_ZX(dfft.Configurations(), world, precision=prec, rank=r)
-        if chunks is not None:
-            pl.setPipelineChunks(chunks)
-        for k, v in (options or {}).items():
-            pl.setOption(k, v)
-        pl.initFFT(dfft.GlobalSize(*shape), dfft.Slab_Partition(P), True, c2c=c2c)
-        size, start = pl.getInSize(), pl.getInStart()
-        blk = orc.fill_block(shape, start, size, 2 if c2c else 1, seed=seed)
-        if center:
-            blk = blk - (CENTER * (1 + 1j) if c2c else CENTER)
-        blk = blk.astype(NPC[prec] if c2c else NPR[prec])
-        plans.append(pl)
-        host_ins.append(blk)
-        ins.append(torch.from_numpy(blk).cuda())
-        outs.append(torch.zeros(pl.getDomainSize() // esz, dtype=CDT[prec], device="cuda"))
+
+    def setup():
+        world = dfft.Comm.local(P) if P > 1 else None
+        plans, ins, outs, host_ins = [], [], [], []
+        for r in range(P):
+            pl = dfft.MPIcuFFT_Slab_Y_Then_ZX(dfft.Configurations(), world, precision=prec, rank=r)
+            if chunks is not None:
+                pl.setPipelineChunks(chunks)
+            for k, v in (options or {}).items():
+                pl.setOption(k, v)
+            pl.initFFT(dfft.GlobalSize(*shape), dfft.Slab_Partition(P), arena is None, c2c=c2c)
+            size, start = pl.getInSize(), pl.getInStart()
+            blk = orc.fill_block(shape, start, size, 2 if c2c else 1, seed=seed)
+            if center:
+                blk = blk - (CENTER * (1 + 1j) if c2c else CENTER)
+            blk = blk.astype(NPC[prec] if c2c else NPR[prec])
+            plans.append(pl)
+            host_ins.append(blk)
+            if arena is not None:
+                arena.domain(pl.getDomainSize())
+                ins.append(arena.input(blk, f"in[{r}]"))
+                outs.append(arena.buffer(pl.getDomainSize(), CDT[prec], name=f"out[{r}]"))
+                arena.work_area(pl, r)
+                continue
+            ins.append(torch.from_numpy(blk).cuda())
+            outs.append(torch.zeros(pl.getDomainSize() // esz, dtype=CDT[prec], device="cuda"))
+        return plans, ins, outs, host_ins
+
+    plans, ins, outs, host_ins = setup() if arena is None else arena.once("slabs.run_yzx", setup)
+    if arena is not None:
+        arena.refill()
     torch.cuda.synchronize()
     fwd = (lambda r: plans[r].execC2C(outs[r], ins[r], dfft.FORWARD)) if c2c else (lambda r: plans[r].execR2C(outs[r], ins[r]))
     with ThreadPoolExecutor(P) as ex:
         list(ex.map(fwd, range(P)))
     torch.cuda.synchronize()
+    if arena is not None:
+        what = f"slabs.run_yzx {shape} P={P} {'C2C' if c2c else 'R2C'} {prec} forward"
+        arena.check_guards(what)
+        arena.check_inputs(what)
     spec = []
     for r in range(P):
         s = plans[r].getOutSize()

@@ -35,8 +35,8 @@ DEDICATED = {"double": [2000], "float": [384, 480, 1200, 1600]}
 SUBSET = {prec: sorted(n for n in set([12, 60, 250, 384, 768, 1536, 720, 1000, 1792, 2000] + DEDICATED[prec]) if n in MIXED[prec]) for prec in PRECISIONS}
 
 
-def plans_2(shape, P1, P2, prec, c2c, layout, chunks=None, cls=dfft.MPIcuFFT_Pencil_Opt1, options=None):
-    return make_plans(shape, P1, P2, prec, c2c, layout, chunks=chunks, cls=cls, options=dict(TWO, **(options or {})))
+def plans_2(shape, P1, P2, prec, c2c, layout, chunks=None, cls=dfft.MPIcuFFT_Pencil_Opt1, options=None, arena=None):
+    return make_plans(shape, P1, P2, prec, c2c, layout, chunks=chunks, cls=cls, options=dict(TWO, **(options or {})), arena=arena)
 
 
 def rows(prec_lengths, *more):

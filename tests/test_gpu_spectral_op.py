@@ -30,7 +30,8 @@ S = dfft.SPECTRAL_OP
 GRIDS = [(1, 1), (2, 1), (1, 2), (2, 2)]
 
 
-def make_plans(shape, P1, P2, prec, c2c, layout, chunks=None, cls=dfft.MPIcuFFT_Pencil_Opt1, options=None):
+def make_plans(shape, P1, P2, prec, c2c, layout, chunks=None, cls=dfft.MPIcuFFT_Pencil_Opt1, options=None, arena=None):
+    """arena (tests/guarded.py): the plans are initialised with allocate=False and get a guarded caller-owned work area each"""
     P = P1 * P2
     world = dfft.Comm.local(P) if P > 1 else None
     plans = []
@@ -42,7 +43,9 @@ def make_plans(shape, P1, P2, prec, c2c, layout, chunks=None, cls=dfft.MPIcuFFT_
         pl.setOption("spectral_layout", layout)
         for k, v in (options or {}).items():
             pl.setOption(k, v)
-        pl.initFFT(dfft.GlobalSize(*shape), dfft.Partition(P1, P2), True, c2c=c2c)
+        pl.initFFT(dfft.GlobalSize(*shape), dfft.Partition(P1, P2), arena is None, c2c=c2c)
+        if arena is not None:
+            arena.work_area(pl, r)
         plans.append(pl)
     return plans
 
@@ -79,14 +82,40 @@ def op_args(plans, prec, m=None, tables=None, reciprocal=False, scale=1.0):
     return [dict(tables=device_tables(pl, prec, tables), reciprocal=reciprocal, scale=scale) for pl in plans]
 
 
-def run_op(plans, prec, c2c, u, m=None, tables=None, reciprocal=False, scale=1.0, args=None):
+def guarded_op_args(arena, plans, prec, m=None, tables=None, reciprocal=False, scale=1.0):
+    """op_args with the array or the tables in guarded input buffers of the arena: a table read outside its entries meets a NaN"""
+    args = []
+    for r, pl in enumerate(plans):
+        if m is not None:
+            t = torch.zeros(pl.getDomainSize() // (16 if prec == "double" else 8), dtype=CDT[prec])
+            pl.spectrumView(t).copy_(torch.from_numpy(spectrum_block(pl, m).astype(NPDT[prec])))
+            args.append(dict(multiplier=arena.input(t.numpy(), f"mult[{r}]"), scale=scale))
+        else:
+            (_, ny, nz), (_, y0, z0) = pl.getOutSize(), pl.getOutStart()
+            ax, ay, az = tables
+            dev = [arena.input(np.asarray(v).astype(NPR[prec]), f"{n}[{r}]") for n, v in (("ax", ax), ("ay", ay[y0:y0 + ny]), ("az", az[z0:z0 + nz]))]
+            args.append(dict(tables=tuple(dev), reciprocal=reciprocal, scale=scale))
+    return args
+
+
+def run_op(plans, prec, c2c, u, m=None, tables=None, reciprocal=False, scale=1.0, args=None, arena=None):
     """execSpectralOp on every rank (one host thread each); returns the ranks' output blocks.  `in` must come back bit for bit.
-    `args`: what op_args made earlier (the caller keeps the device buffers)"""
+    `args`: what op_args made earlier (the caller keeps the device buffers).  arena (tests/guarded.py; the plans from make_plans with
+    the same arena): `in`, `out` and the multiplier come from it at the first call and are used again at every later one, `out` and
+    the work areas are refilled before the exec, the guards and every input are checked after it"""
     P = len(plans)
     dt = NPDT[prec] if c2c else NPR[prec]
-    ins = [torch.from_numpy(in_block(pl, u).astype(dt)).cuda() for pl in plans]
+    if arena is not None:
+        def setup():
+            ins = [arena.input(in_block(pl, u).astype(dt), f"in[{r}]") for r, pl in enumerate(plans)]
+            outs = [arena.buffer(t.numel() * t.element_size(), t.dtype, name=f"out[{r}]").reshape(t.shape) for r, t in enumerate(ins)]
+            return ins, outs, guarded_op_args(arena, plans, prec, m, tables, reciprocal, scale)
+        ins, outs, args = arena.once("run_op", setup)
+        arena.refill()
+    else:
+        ins = [torch.from_numpy(in_block(pl, u).astype(dt)).cuda() for pl in plans]
+        outs = [torch.full_like(t, float("nan")) for t in ins]
     before = [t.cpu().numpy().tobytes() for t in ins]
-    outs = [torch.full_like(t, float("nan")) for t in ins]
     if args is None:
         args = op_args(plans, prec, m, tables, reciprocal, scale)
     torch.cuda.synchronize()
@@ -95,6 +124,9 @@ def run_op(plans, prec, c2c, u, m=None, tables=None, reciprocal=False, scale=1.0
     torch.cuda.synchronize()
     for r in range(P):
         assert ins[r].cpu().numpy().tobytes() == before[r], f"rank {r}: execSpectralOp modified its input"
+    if arena is not None:
+        arena.check_guards("execSpectralOp")
+        arena.check_inputs("execSpectralOp")
     return [t.cpu().numpy() for t in outs]
 
 

@@ -123,20 +123,29 @@ def test_distributed_long_bluestein_axes_vs_oracle(shape, P1, P2, chunks, c2c):
     check_forward_blocks(plans, spec, want, prec, g.size, zero_mean=False)
 
 
-def single(shape, prec, c2c, options=None, seed=5, center=False):
+def single(shape, prec, c2c, options=None, seed=5, center=False, arena=None):
+    """arena: as in test_gpu_parity.run_single"""
     cdt = torch.complex128 if prec == "double" else torch.complex64
-    plan = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), precision=prec)
-    for k, v in (options or {}).items():
-        plan.setOption(k, v)
-    plan.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(1, 1), True, c2c=c2c)
     esz = 16 if prec == "double" else 8
     g = orc.fill_block(shape, (0, 0, 0), shape, 2 if c2c else 1, seed=seed)
     if center:
         g = g - (CENTER * (1 + 1j) if c2c else CENTER)
     g = g.astype(NPDT[prec]) if c2c else g.astype(np.float64 if prec == "double" else np.float32)
-    d_in = torch.from_numpy(g).cuda()
-    d_out = torch.zeros(plan.getDomainSize() // esz, dtype=cdt, device="cuda")
-    d_back = torch.zeros_like(d_in)
+
+    def setup():
+        plan = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), precision=prec)
+        for k, v in (options or {}).items():
+            plan.setOption(k, v)
+        plan.initFFT(dfft.GlobalSize(*shape), dfft.Pencil_Partition(1, 1), arena is None, c2c=c2c)
+        if arena is not None:
+            return (plan,) + arena.plan_buffers(plan, g, cdt)
+        d_in = torch.from_numpy(g).cuda()
+        return plan, d_in, torch.zeros(plan.getDomainSize() // esz, dtype=cdt, device="cuda"), torch.zeros_like(d_in)
+
+    plan, d_in, d_out, d_back = setup() if arena is None else arena.once("two_level.single", setup)
+    what = f"two_level.single {shape} {prec} {'C2C' if c2c else 'R2C'} {options or ''}"
+    if arena is not None:
+        arena.refill()
     torch.cuda.synchronize()
     if c2c:
         plan.execC2C(d_out, d_in, dfft.FORWARD)
@@ -145,12 +154,18 @@ def single(shape, prec, c2c, options=None, seed=5, center=False):
     s = plan.getOutSize()
     got = d_out[:s[0] * s[1] * s[2]].cpu().numpy().reshape(s)
     assert np.array_equal(d_in.cpu().numpy(), g), "forward must not modify its input"
+    if arena is not None:
+        arena.check_guards(what + " forward")
+        arena.check_inputs(what + " forward")
+        arena.refill(keep=[d_out])
     torch.cuda.synchronize()
     if c2c:
         plan.execC2C(d_back, d_out, dfft.INVERSE)
     else:
         plan.execC2R(d_back, d_out)
     torch.cuda.synchronize()
+    if arena is not None:
+        arena.check_guards(what + " inverse")
     return g, got, d_back.cpu().numpy()
 
 

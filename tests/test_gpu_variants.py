@@ -37,13 +37,16 @@ def spectrum(shape, prec, real, center=False):
     return orc.fft3d_c2c(g.astype(NPDT[prec]).astype(np.complex128), -1)
 
 
-def check(shape, P1, P2, prec, v, real, center=False, label=None):
-    """center: the zero-mean input, where the per-entry bound is asserted at fp32 too (parity_metric.py)"""
+def check(shape, P1, P2, prec, v, real, center=False, label=None, arena=None, spectra=None):
+    """center: the zero-mean input, where the per-entry bound is asserted at fp32 too (parity_metric.py); arena: handed to the runner
+    (tests/guarded.py); spectra: a list that receives the ranks' spectrum blocks"""
     opts = {"variant_" + k: v for k in PASSES}
     if real:
-        plans, ins, spec, backs = run_distributed_real(shape, P1, P2, prec, options=opts, field=real_field(shape, True) if center else None)
+        plans, ins, spec, backs = run_distributed_real(shape, P1, P2, prec, options=opts, field=real_field(shape, True) if center else None, arena=arena)
     else:
-        plans, ins, spec, backs = run_distributed(shape, P1, P2, prec, options=opts, center=center)
+        plans, ins, spec, backs = run_distributed(shape, P1, P2, prec, options=opts, center=center, arena=arena)
+    if spectra is not None:
+        spectra[:] = spec
     want = spectrum(shape, prec, real, center)
     n3 = float(np.prod(shape))
     per_entry = check_forward_blocks(plans, spec, want, prec, int(n3), zero_mean=center, label=label)
