@@ -23,6 +23,7 @@ Peer2Peer, All2All = 0, 1
 Sync, Streams, MPI_Type = 0, 1, 2
 FORWARD, INVERSE = -1, 1
 SPECTRAL_OP = 2      # DFFT_SPECTRAL_OP: the chain of execSpectralOp in debugChain / debugTrace
+SPECTRAL_OPS = 3     # DFFT_SPECTRAL_OPS: the chain of execSpectralOps for as many outputs as option spectral_outputs says
 
 
 class GlobalSize:
@@ -385,6 +386,32 @@ class MPIcuFFT:
         or factors = (cx, cy, cz): complex device tables with Nx, yo, zs entries, any but not all of them None (a factor of 1),
         m = scale * cx * cy * cz -- together with tables, m = scale * cx * cy * cz * (ax + ay + az), resp. / (ax + ay + az) with
         reciprocal=True.  All tables are local to the rank's spectrum block (wavenumbers() gives its kx, ky, kz)."""
+        op = self._spectral_op(multiplier, tables, reciprocal, scale, factors)
+        check(lib().dfft_exec_spectral_op(self._h, _ptr(out), _ptr(in_), C.byref(op)))
+
+    def execSpectralOps(self, outs, in_, ops):
+        """outs[j] = IFFT(m_j * FFT(in_)) for every j, unnormalised, with one forward half for all of them: the z and y passes and the
+        forward exchanges run once, the fused x kernel and the inverse half once per output (dfft_exec_spectral_ops) -- the components
+        of a gradient, a field and its Laplacian.  The plan needs setOption("spectral_outputs", K) with K >= len(outs) next to
+        spectral_op, before initFFT.  ops: one dict per output with the keywords of execSpectralOp (multiplier, tables, reciprocal,
+        scale, factors).  Every outs[j] and in_ are blocks of the input layout, all different; in_ is only read.  Each output is bit for
+        bit what execSpectralOp gives with the same operator."""
+        from ._lib import SpectralOp
+        outs, ops = list(outs), list(ops)
+        if len(outs) != len(ops):
+            raise DfftError("execSpectralOps takes one operator per output")
+        for op in ops:
+            extra = set(op) - {"multiplier", "tables", "reciprocal", "scale", "factors"}
+            if extra:
+                raise DfftError(f"execSpectralOps: unknown operator keyword {sorted(extra)[0]}")
+        c_ops = (SpectralOp * max(1, len(ops)))(*[self._spectral_op(op.get("multiplier"), op.get("tables"), op.get("reciprocal", False),
+                                                                    op.get("scale", 1.0), op.get("factors")) for op in ops])
+        c_outs = (C.c_void_p * max(1, len(outs)))(*[_ptr(o).value for o in outs])
+        check(lib().dfft_exec_spectral_ops(self._h, len(outs), c_outs, _ptr(in_), c_ops))
+
+    @staticmethod
+    def _spectral_op(multiplier, tables, reciprocal, scale, factors):
+        """the dfft_spectral_op of execSpectralOp's keywords"""
         from ._lib import SpectralOp
         if multiplier is not None and (tables is not None or factors is not None):
             raise DfftError("execSpectralOp takes either multiplier= or tables= / factors=")
@@ -405,7 +432,7 @@ class MPIcuFFT:
             op = SpectralOp(2 if reciprocal else 1, float(scale), None, val(ax), val(ay), val(az))
         else:
             op = SpectralOp(0, float(scale), val(multiplier), None, None, None)
-        check(lib().dfft_exec_spectral_op(self._h, _ptr(out), _ptr(in_), C.byref(op)))
+        return op
 
     def wavenumbers(self):
         """(kx, ky, kz): the integer wavenumbers of the rank's spectrum block as host int64 arrays, in the wrapped order

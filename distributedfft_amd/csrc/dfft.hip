@@ -64,11 +64,10 @@ static int launch(dfft_plan *p, const Launch &L, int form, int axis, bool conj, 
     return launch_axis(p->prec, ax, A, variant, real_mode, NK, static_cast<char *>(p->work_d) + p->lv_off, p->lv_bytes, p->TL, stream);
 }
 
-// one launch of group xx (fft_spectral_kernel): forward x pass, the multiplier p->op, inverse x pass
-static int launch_spectral(dfft_plan *p, const Launch &L, const char *in, char *out, hipStream_t stream)
+// one launch of group xx (fft_spectral_kernel): forward x pass, the multiplier `op`, inverse x pass
+static int launch_spectral(dfft_plan *p, const Launch &L, const dfft_spectral_op &op, const char *in, char *out, hipStream_t stream)
 {
     if (L.args.ntiles == 0) return 0;
-    const dfft_spectral_op &op = p->op;
     const size_t real = p->esz / 2;
     PassArgs A = L.args;
     A.in = in + L.in_off; A.out = out + L.out_off; A.tw = p->ax[2].tw; A.debug = 0;
@@ -169,6 +168,7 @@ static const Chain &chain_of(const dfft_plan *p, int direction, int dims)
 {
     const Pipeline &pl = p->pl;
     if (direction == DFFT_SPECTRAL_OP) return pl.spec;      // (dfft_exec_spectral_op; empty without option spectral_op)
+    if (direction == DFFT_SPECTRAL_OPS) return pl.spec_multi;      // (dfft_exec_spectral_ops; empty while option spectral_outputs is 1)
     const bool fwd = direction != DFFT_INVERSE;
     if (dims == 3 && one_rank_alternative(p) && !(fwd ? pl.one_fwd : pl.one_inv).steps.empty()) return fwd ? pl.one_fwd : pl.one_inv;
     return fwd ? pl.fwd[dims - 1] : pl.inv[dims - 1];
@@ -258,6 +258,7 @@ struct HipSink {
     }
     char *buf(int b) const
     {
+        if (b < BUF_IN) return static_cast<char *>(p->outs[-b - 2]);      // output j >= 1 of a multi-output chain (buf_output)
         return b == BUF_IN ? const_cast<char *>(static_cast<const char *>(in)) : b == BUF_OUT ? static_cast<char *>(out)
                                                                                : static_cast<char *>(p->work_d) + (size_t)b * p->domainsize;
     }
@@ -266,7 +267,7 @@ struct HipSink {
         const Step &t = st[(size_t)step];
         const Group &g = p->pl.groups[t.group];
         if (log) log->push_back(trace_launch(p, st, step, chunk, k, s));
-        if (t.group == G_XX) return launch_spectral(p, g.L[(size_t)k], buf(t.src), buf(t.dst), S[s]);
+        if (t.group == G_XX) return launch_spectral(p, g.L[(size_t)k], p->ops[spectral_output_of(step)], buf(t.src), buf(t.dst), S[s]);
         return launch(p, g.L[(size_t)k], t.form, g.axis, t.conj, buf(t.src), buf(t.dst), S[s]);
     }
     int xchg(int step, int chunk, int s, int ready)
@@ -366,14 +367,19 @@ template <typename Sink> static int schedule_chain(const dfft_plan *p, const Cha
     return 0;
 }
 
-static int trace_slot(int direction) { return direction == DFFT_SPECTRAL_OP ? 2 : direction == DFFT_INVERSE ? 1 : 0; }
-
-// Runs one execution chain: schedule_chain through the sink that issues HIP calls
-static int run_chain(dfft_plan *p, int direction, int dims, void *out, const void *in)
+static int trace_slot(int direction)
 {
-    const Chain &ch = chain_of(p, direction, dims);
+    return direction == DFFT_SPECTRAL_OPS ? 3 : direction == DFFT_SPECTRAL_OP ? 2 : direction == DFFT_INVERSE ? 1 : 0;
+}
+
+// Runs one execution chain: schedule_chain through the sink that issues HIP calls.  `prefix`: the chain to run where it is not
+// chain_of's (the first steps of Pipeline::spec_multi for fewer outputs than the plan was built for)
+static int run_chain(dfft_plan *p, int direction, int dims, void *out, const void *in, const Chain *prefix = nullptr)
+{
+    const Chain &ch = prefix ? *prefix : chain_of(p, direction, dims);
     if (ch.steps.empty())
         return direction == DFFT_SPECTRAL_OP ? fail(ERR_STATE, "plan was initialised without option spectral_op")
+               : direction == DFFT_SPECTRAL_OPS ? fail(ERR_STATE, "set spectral_outputs before dfft_init")
                                              : fail(ERR_UNSUPPORTED, "the Y_Then_ZX sequence is forward only (as in the reference)");
     const StreamUse use = streams_of(p, ch);
     p->nspans = 0; p->last_dir = direction == DFFT_INVERSE ? DFFT_INVERSE : DFFT_FORWARD;
@@ -596,6 +602,7 @@ static int *option_slot(Options &o, const std::string &k)
     if (k == "graph") return &o.graph;
     if (k == "spectral_layout") return &o.spectral;
     if (k == "spectral_op") return &o.spectral_op;
+    if (k == "spectral_outputs") return &o.spectral_outputs;
     if (k == "compute_streams") return &o.compute_streams;
     if (k == "trace") return &o.trace;
     for (int i = 0; i < 6; i++) {
@@ -822,6 +829,14 @@ int dfft_init(dfft_plan *p, size_t Nx, size_t Ny, size_t Nz, int P1, int P2, int
     if (p->opt.spectral_op) {
         TRY(admit_spectral_op(p, zyx || yzx));
         p->worksize_d += p->domainsize;      // the slice that stands in for `out` (forward half) and `in` (inverse half)
+    }
+    if (p->opt.spectral_outputs < 1 || p->opt.spectral_outputs > DFFT_SPECTRAL_MAX_OUTPUTS)
+        return fail(ERR_ARG, "spectral_outputs: 1 to " + std::to_string(DFFT_SPECTRAL_MAX_OUTPUTS));
+    if (p->opt.spectral_outputs > 1) {
+        if (!p->opt.spectral_op) return fail(ERR_ARG, "spectral_outputs: needs option spectral_op = 1 or 2");
+        // the multi-output chain never writes the slice xx reads: one more slice wherever the single-output chain writes it again
+        // (every grid but a P1 x P2 pencil: pipeline.hip), whatever the number of outputs
+        if (P1 == 1 || P2 == 1) p->worksize_d += p->domainsize;
     }
     // (one rank: the inverse of an x-contiguous spectrum cannot be the forward launches with conjugation -- their input is the natural grid)
     p->spectral_mirror = p->opt.spectral && p->nranks == 1;
@@ -1057,21 +1072,19 @@ int dfft_spectral_op_supported(int precision, size_t Nx, int option_value)
     return spectral_kernel_for(precision, ax, option_value, nullptr) != SPECTRAL_NONE ? 1 : 0;
 }
 
-int dfft_exec_spectral_op(dfft_plan *p, void *out, const void *in, const dfft_spectral_op *op)
+// The operator of a spectral-operator exec: checks `op` (`which`: "" or the " ops[j]" the message names) and copies the fields its
+// kind reads into `dst`.  One function for dfft_exec_spectral_op and every operator of dfft_exec_spectral_ops
+static int take_spectral_op(const dfft_plan *p, const dfft_spectral_op *op, const std::string &which, dfft_spectral_op &dst)
 {
-    if (p && p->initialized && p->pl.spec.steps.empty())
-        return fail(ERR_STATE, "plan was initialised without option spectral_op (set it before dfft_init)");
-    TRY(check_ready(p));
-    if (!out || !in || !op) return fail(ERR_ARG, "null buffer or operator");
-    if (out == in) return fail(ERR_ARG, "spectral_op: out == in is not supported");
+    const std::string pre = "spectral_op" + which + ": ";
     if (op->kind < 0 || op->kind > 5)
-        return fail(ERR_ARG, "spectral_op: kind must be 0 (array), 1 (sum of tables), 2 (reciprocal of the sum), 3 (product of factor tables), "
-                             "4 (product times the sum) or 5 (product over the sum)");
+        return fail(ERR_ARG, pre + "kind must be 0 (array), 1 (sum of tables), 2 (reciprocal of the sum), 3 (product of factor tables), "
+                                   "4 (product times the sum) or 5 (product over the sum)");
     // the fields a kind does not use are never read: cx, cy, cz were appended, a caller of kinds 0 .. 2 may hold the six-field struct
     const bool sums = op->kind == 1 || op->kind == 2 || op->kind == 4 || op->kind == 5, factors = op->kind >= 3;
-    if (op->kind == 0 && !op->mult) return fail(ERR_ARG, "spectral_op: null multiplier");
-    if (sums && (!op->ax || !op->ay || !op->az)) return fail(ERR_ARG, "spectral_op: null multiplier (kinds 1, 2, 4 and 5 need all of ax, ay, az)");
-    if (factors && !op->cx && !op->cy && !op->cz) return fail(ERR_ARG, "spectral_op: null multiplier (kinds 3, 4 and 5 need at least one of cx, cy, cz)");
+    if (op->kind == 0 && !op->mult) return fail(ERR_ARG, pre + "null multiplier");
+    if (sums && (!op->ax || !op->ay || !op->az)) return fail(ERR_ARG, pre + "null multiplier (kinds 1, 2, 4 and 5 need all of ax, ay, az)");
+    if (factors && !op->cx && !op->cy && !op->cz) return fail(ERR_ARG, pre + "null multiplier (kinds 3, 4 and 5 need at least one of cx, cy, cz)");
     if (op->kind == 0) {
         // one tile per workgroup: the kernel adds 32-bit lane offsets (t*MK + l*ME elements) to a scalar base per point.  G and the threads
         // per line are the axis pass's: a configuration of the fused kernel's own (spectral_mixed.inc) has the same G and, at G = 1, no more
@@ -1080,14 +1093,50 @@ int dfft_exec_spectral_op(dfft_plan *p, void *out, const void *in, const dfft_sp
         const Launch *L = p->pl.groups[G_XX].L.empty() ? nullptr : &p->pl.groups[G_XX].L[0];
         if (L && pass_info(p->prec, (int)p->Nx, &pi) && pi.G == 1 &&
             ((uint64_t)(pi.N / pi.E) * L->args.MK + (uint64_t)pi.TL * L->args.ME) * p->esz >= (1ull << 32))
-            return fail(ERR_UNSUPPORTED, "spectral_op: the multiplier block is too large for the kernel's 32-bit lane offsets");
+            return fail(ERR_UNSUPPORTED, pre + "the multiplier block is too large for the kernel's 32-bit lane offsets");
     }
-    p->op = dfft_spectral_op{};
-    p->op.kind = op->kind; p->op.scale = op->scale;
-    if (op->kind == 0) p->op.mult = op->mult;
-    if (sums) { p->op.ax = op->ax; p->op.ay = op->ay; p->op.az = op->az; }
-    if (factors) { p->op.cx = op->cx; p->op.cy = op->cy; p->op.cz = op->cz; }
+    dst = dfft_spectral_op{};
+    dst.kind = op->kind; dst.scale = op->scale;
+    if (op->kind == 0) dst.mult = op->mult;
+    if (sums) { dst.ax = op->ax; dst.ay = op->ay; dst.az = op->az; }
+    if (factors) { dst.cx = op->cx; dst.cy = op->cy; dst.cz = op->cz; }
+    return 0;
+}
+
+int dfft_exec_spectral_op(dfft_plan *p, void *out, const void *in, const dfft_spectral_op *op)
+{
+    if (p && p->initialized && p->pl.spec.steps.empty())
+        return fail(ERR_STATE, "plan was initialised without option spectral_op (set it before dfft_init)");
+    TRY(check_ready(p));
+    if (!out || !in || !op) return fail(ERR_ARG, "null buffer or operator");
+    if (out == in) return fail(ERR_ARG, "spectral_op: out == in is not supported");
+    TRY(take_spectral_op(p, op, "", p->ops[0]));
     TRY(run_chain(p, DFFT_SPECTRAL_OP, 3, out, in));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int dfft_exec_spectral_ops(dfft_plan *p, int nout, void *const *outs, const void *in, const dfft_spectral_op *ops)
+{
+    if (p && p->initialized && p->pl.spec_multi.steps.empty()) return fail(ERR_STATE, "set spectral_outputs before dfft_init");
+    TRY(check_ready(p));
+    if (nout < 1 || nout > p->opt.spectral_outputs)
+        return fail(ERR_ARG, "spectral_ops: nout must be 1 to " + std::to_string(p->opt.spectral_outputs) + " (option spectral_outputs)");
+    if (!outs || !in || !ops) return fail(ERR_ARG, "null buffer or operator");
+    for (int j = 0; j < nout; j++) {
+        if (!outs[j]) return fail(ERR_ARG, "null buffer or operator");
+        if (outs[j] == in) return fail(ERR_ARG, "spectral_ops: outs[" + std::to_string(j) + "] == in is not supported");
+        for (int i = 0; i < j; i++)
+            if (outs[i] == outs[j]) return fail(ERR_ARG, "spectral_ops: outs[" + std::to_string(i) + "] == outs[" + std::to_string(j) + "]");
+    }
+    for (int j = 0; j < nout; j++) {
+        TRY(take_spectral_op(p, &ops[j], " ops[" + std::to_string(j) + "]", p->ops[j]));
+        p->outs[j] = outs[j];
+    }
+    // the slices do not depend on the number of outputs: fewer of them are the first steps of the plan's chain
+    Chain ch = p->pl.spec_multi;
+    ch.steps.resize((size_t)(2 + 3 * nout));
+    TRY(run_chain(p, DFFT_SPECTRAL_OPS, 3, outs[0], in, &ch));
     HIP_TRY(hipStreamSynchronize(p->stream));
     return 0;
 }
@@ -1213,7 +1262,7 @@ int dfft_debug_get_pass(const dfft_plan *p, const char *name, int index, dfft_pa
 int dfft_debug_get_chain(const dfft_plan *p, int direction, int dims, dfft_chain_step *steps, int capacity, int *count)
 {
     if (!p || !p->initialized) return fail(ERR_STATE, "plan not initialised");
-    const bool spec = direction == DFFT_SPECTRAL_OP && dims == 3;
+    const bool spec = (direction == DFFT_SPECTRAL_OP || direction == DFFT_SPECTRAL_OPS) && dims == 3;
     if (dims < 1 || dims > 3 || (direction != DFFT_FORWARD && direction != DFFT_INVERSE && !spec)) return fail(ERR_ARG, "bad direction or dims");
     const Chain &ch = chain_of(p, direction, dims);
     const std::vector<Step> &st = ch.steps;
@@ -1234,7 +1283,7 @@ int dfft_debug_get_chain(const dfft_plan *p, int direction, int dims, dfft_chain
 int dfft_debug_trace_chain(const dfft_plan *p, int direction, int dims, dfft_trace_op *ops, int capacity, int *count)
 {
     if (!p || !p->initialized) return fail(ERR_STATE, "plan not initialised");
-    const bool spec = direction == DFFT_SPECTRAL_OP && (dims == 3 || dims == 0);
+    const bool spec = (direction == DFFT_SPECTRAL_OP || direction == DFFT_SPECTRAL_OPS) && (dims == 3 || dims == 0);
     if (dims < 0 || dims > 3 || (direction != DFFT_FORWARD && direction != DFFT_INVERSE && !spec)) return fail(ERR_ARG, "bad direction or dims");
     std::vector<dfft_trace_op> dry;
     if (dims > 0) {

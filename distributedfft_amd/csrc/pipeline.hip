@@ -61,7 +61,7 @@ static std::vector<Launch> &group(Pipeline &pl, int g, size_t n)
 static void clear(Pipeline &pl)
 {
     for (auto &g : pl.groups) g.L.clear();
-    for (Chain *c : {&pl.fwd[0], &pl.fwd[1], &pl.fwd[2], &pl.inv[0], &pl.inv[1], &pl.inv[2], &pl.one_fwd, &pl.one_inv, &pl.spec}) *c = Chain();
+    for (Chain *c : {&pl.fwd[0], &pl.fwd[1], &pl.fwd[2], &pl.inv[0], &pl.inv[1], &pl.inv[2], &pl.one_fwd, &pl.one_inv, &pl.spec, &pl.spec_multi}) *c = Chain();
     pl.single = false;
 }
 
@@ -302,6 +302,32 @@ int build_pipeline(dfft_plan *p, Pipeline &pl)
                          {G_IY, FORM_INV, isrc, idst, -1, x1, true, 1, false, DFFT_INVERSE},
                          {G_IZ, zi, zsrc, BUF_OUT, -1, 0, P2 == 1, 1, false, DFFT_INVERSE}};
         pl.spec.split = true;
+        // Option spectral_outputs = K >= 2: fz, fy as above, then K times (xx, y^-1, z^-1), triple j for output j.  Nothing may write xsrc
+        // once the forward half has filled it, and the chain above does so in three grid classes (y^-1: one rank and slab; exchange 1
+        // backwards: 1 x P2).  There the write moves to one more slice F = E + 1 (dfft_init adds it to the work area); a P1 x P2 pencil
+        // keeps every slice:
+        //              ysrc ydst xsrc xd  isrc idst zsrc
+        //   one rank    E    0    0   1    1    F    F        (F in the place of 0)
+        //   slab        E    0    1   0    E    F    F        (F in the place of 1)
+        //   1 x P2      0    1    1   0    0    E    F        (F in the place of 1)
+        //   P1 x P2     0    1    2   0    1    E    0        (unchanged: nothing writes slice 2 after exchange 2)
+        // The assignment is the same for every triple and every K.  xx of output j + 1 writes xd again, whose last reader is y^-1 of
+        // output j (exchange 2 backwards on a pencil or slab), and on a P1 x P2 pencil xd is also the zsrc that z^-1 of output j reads:
+        // xx waits for the whole step before it, z^-1 of output j, which is behind all of them.  isrc, idst and zsrc are written again
+        // behind xx of output j + 1 (exchange 2 backwards, y^-1, exchange 1 backwards), so behind that wait too.
+        // tests/test_cpu_spectral_multi.py replays the chain on NaN-filled slices and runs the schedule checker on every case.
+        if (p->opt.spectral_outputs > 1) {
+            const bool pencil = P1 > 1 && P2 > 1;
+            const int F = E + 1;
+            const int midst = pencil || P2 > 1 ? idst : F, mzsrc = pencil ? zsrc : F;
+            pl.spec_multi.steps = {pl.spec.steps[0], pl.spec.steps[1]};
+            for (int j = 0; j < p->opt.spectral_outputs; j++) {
+                pl.spec_multi.steps.push_back({G_XX, FORM_FIXED, xsrc, xd, -1, x2, true, 1, false, DFFT_INVERSE});
+                pl.spec_multi.steps.push_back({G_IY, FORM_INV, isrc, midst, -1, x1, true, 1, false, DFFT_INVERSE});
+                pl.spec_multi.steps.push_back({G_IZ, zi, mzsrc, buf_output(j), -1, 0, P2 == 1, 1, false, DFFT_INVERSE});
+            }
+            pl.spec_multi.split = true;
+        }
     }
     // partial transforms: d = 1 stops after the z pass with the natural stage layout [xs][ys][Nzc]; d = 2 after the y pass with
     // [xs][Ny][zs] (z contiguous)

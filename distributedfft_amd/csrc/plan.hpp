@@ -85,7 +85,10 @@ struct Group {
 };
 
 // One step of an execution chain: the launches of a group, chunk by chunk, with the exchange after each chunk (run_chain, dfft.hip).
-enum Buffer { BUF_IN = -2, BUF_OUT = -1 };     // and k >= 0: work-area slice k
+enum Buffer { BUF_IN = -2, BUF_OUT = -1 };     // and k >= 0: work-area slice k; -(2 + j): output j >= 1 of a multi-output chain
+inline int buf_output(int j) { return j == 0 ? BUF_OUT : -(2 + j); }
+// the output a step of a spectral-operator chain belongs to (Pipeline::spec: always 0; spec_multi: by position)
+inline int spectral_output_of(int step) { return step < 2 ? 0 : (step - 2) / 3; }
 enum LineForm {
     FORM_FWD,         // complex lines, kernel configuration vfwd[axis]
     FORM_INV,         // complex lines, vinv[axis]
@@ -121,6 +124,10 @@ struct Pipeline {
     // option spectral_op (dfft_exec_spectral_op): z -> ex1 -> y -> ex2 -> xx -> ex2^-1 -> y^-1 -> ex1^-1 -> z^-1 on work slices alone
     // (`in` is only read, `out` only written by z^-1); empty without the option
     Chain spec;
+    // option spectral_outputs = K >= 2 (dfft_exec_spectral_ops): one forward half, K inverse halves -- fz, fy, then K times xx, iy, iz.
+    // The step at position 2 + 3 j + {0, 1, 2} belongs to output j (spectral_output_of): its xx runs operator j, its iz writes output
+    // j.  The slices do not depend on K, so an exec of nout < K outputs runs the first 2 + 3 nout steps.  Empty when K == 1
+    Chain spec_multi;
     bool single = false;                       // the z, x, y order is built
     size_t single_work_elems = 0;              // size of the padded L2 buffer
     std::vector<A2A> f1, f2, i2, i1;          // per chunk exchange tables
@@ -161,6 +168,8 @@ struct Options {
                              // touches the point-major layout whose strided read is the slowest pass of every multi-rank plan
     int spectral_op = 0;     // 1 / 2 (2: mixed-radix x lengths as well): the plan also builds the fused forward-multiply-inverse chain (Pipeline::spec, group xx) and one more
                              // work slice for it; 0: nothing of it exists
+    int spectral_outputs = 1; // 1 .. 8 (DFFT_SPECTRAL_MAX_OUTPUTS), needs spectral_op: from 2 on the plan also builds Pipeline::spec_multi for
+                             // dfft_exec_spectral_ops and, where that chain needs it, one more work slice; 1: nothing of it exists
     int compute_streams = -1; // 2: the pipeline chunks of a pass alternate over two compute streams, so that the drain of chunk c
                              // overlaps the ramp of chunk c + 1 (a chunk launch of 0.1-0.2 ms pays ~20 us of launch / drain / ramp when
                              // the chunks queue up behind each other on one stream).  -1 = by measurement
@@ -209,8 +218,10 @@ struct dfft_plan {
     std::vector<TimedSpan> spans;
     size_t nspans = 0;
     int last_dir = -1;
-    std::vector<dfft_trace_op> trace_log[3];   // option trace: what the last forward / inverse / spectral-operator exec issued
-    dfft_spectral_op op{};                     // the multiplier of the spectral-operator exec being enqueued
+    std::vector<dfft_trace_op> trace_log[4];   // option trace: what the last forward / inverse / spectral-operator / multi-output exec issued
+    // the spectral-operator exec being enqueued: the multiplier of output j and, for j >= 1, its buffer (output 0 is the exec's `out`)
+    dfft_spectral_op ops[DFFT_SPECTRAL_MAX_OUTPUTS] = {};
+    void *outs[DFFT_SPECTRAL_MAX_OUTPUTS] = {};
     int spectral_kernel = 0;                   // option spectral_op: the fused x kernel dfft_init found (dfft::SpectralKernel, axis.hpp)
     // hipGraph replay of single-rank execs (launch-bound small grids): one instantiated graph per (operation, in, out)
     struct GraphEntry { int kind; const void *in; void *out; int uses; hipGraphExec_t exec; };

@@ -58,6 +58,8 @@ enum dfft_precision { DFFT_F32 = 0, DFFT_F64 = 1 };   /* template parameter T = 
 enum dfft_direction { DFFT_FORWARD = -1, DFFT_INVERSE = 1 };
 /* third "direction" of the debug interface (dfft_debug_get_chain, dfft_debug_trace_chain): the chain of dfft_exec_spectral_op */
 #define DFFT_SPECTRAL_OP 2
+#define DFFT_SPECTRAL_OPS 3          /* debug "direction": the multi-output chain for the option's value */
+#define DFFT_SPECTRAL_MAX_OUTPUTS 8
 
 /* struct Configurations, include/params.hpp:83-93.  comm/send method enums are accepted and
  * recorded; the device exchange always runs as one grouped all-to-all per exchange. */
@@ -204,6 +206,13 @@ int dfft_get_pipeline_chunks(const dfft_plan *plan);
  *                      native lengths left out), running the native chain -- ERR_UNSUPPORTED for an x length on the Bluestein or
  *                      two-level kernel ("native_mixed" = 0, "two_level" = 1, any other length).  A power-of-two x length gives the same
  *                      plan under 1 and 2.  Any other value: ERR_ARG.
+ *   "spectral_outputs" 1 (default) .. 8 (DFFT_SPECTRAL_MAX_OUTPUTS), before dfft_init; from 2 on it needs "spectral_op" = 1 or 2.  K >= 2: the
+ *                      plan also builds the chain of dfft_exec_spectral_ops -- one forward half (z, y, both exchanges), then per output
+ *                      the fused x launch with that output's operator and the inverse y and z passes with their exchanges -- out of the
+ *                      launches it already has.  It costs at most one more domain-sized slice of the work area, the same for every K
+ *                      (dfft_work_size_device reports it; none on a P1 x P2 pencil with both factors above 1), because that chain never
+ *                      overwrites the slice the fused launch reads.  With 1 no size, launch or chain of the plan differs.  Any other
+ *                      value, or K >= 2 without "spectral_op": ERR_ARG at dfft_init.
  *   "graph"            1: a single-rank plan replays the kernel launches of an exec as one hipGraph from the second call
  *                      with the same (operation, in, out) on; 0 (default): plain launches -- measured 6-8 us faster per
  *                      exec on ROCm 7.2 (profiles/r2_graph_latency.txt)
@@ -295,6 +304,16 @@ typedef struct dfft_spectral_op {
     const void *cx, *cy, *cz;   /* kind 3, 4, 5 (read for no other kind) */
 } dfft_spectral_op;
 int dfft_exec_spectral_op(dfft_plan *plan, void *out, const void *in, const dfft_spectral_op *op);
+/* new: several operators on one input, outs[j] = IFFT(ops[j] * FFT(in)) for j < nout -- the components of a gradient, a field and its
+ * Laplacian -- with ONE forward half: the z and y passes and both forward exchanges run once, the fused x launch and the inverse half
+ * once per output.  4 + 6 nout trips of a domain-sized buffer through memory and 2 + 2 nout exchanges instead of the 10 nout and 4 nout
+ * of nout calls of dfft_exec_spectral_op (table forms), and every outs[j] is bit for bit what that call gives.  The plan needs
+ * option "spectral_outputs" >= nout (ERR_STATE while the option is 1: "set spectral_outputs before dfft_init"); nout = 1 is valid on such a
+ * plan.  Every outs[j] is a block of the input layout like `out` above; `in` is only read.  Footprint: `in`, the outs[j] and the
+ * dfft_work_size_device() bytes of the work area.  ERR_ARG: nout < 1 or above the option's value, a null pointer, two equal outputs, an
+ * output equal to `in`, an ops[j] that dfft_exec_spectral_op would refuse (the message names j; the same checks, the 32-bit lane-offset
+ * bound of kind 0 included: ERR_UNSUPPORTED).  Blocking; collective on a multi-rank plan, every rank with the same nout. */
+int dfft_exec_spectral_ops(dfft_plan *plan, int nout, void *const *outs, const void *in, const dfft_spectral_op *ops);
 /* 1 if dfft_init with default options accepts an x length of Nx points under option "spectral_op" = option_value (1 or 2), else 0
  * (also for another option_value or precision).  Host only: no device is touched; loads libdfft_amd_any.so when Nx is not a power of two. */
 int dfft_spectral_op_supported(int precision, size_t Nx, int option_value);
@@ -394,7 +413,8 @@ typedef struct dfft_chain_step {
     char group[8];          /* launch group, as dfft_debug_get_pass names it */
     int32_t axis;           /* 0 z, 1 y, 2 x */
     int32_t launches, per_chunk;
-    int32_t src, dst;       /* -2 the exec's input, -1 its output, k >= 0 slice k of the work area (dfft_domain_size bytes each) */
+    int32_t src, dst;       /* -2 the exec's input, -1 its output (output 0 of dfft_exec_spectral_ops; -(2 + j): its output j >= 1), k >= 0
+                             * slice k of the work area (dfft_domain_size bytes each) */
     int32_t conj;           /* 1: launched with conjugation whatever the descriptor's swap says */
     int32_t form;           /* 0 / 1 / 2 complex lines (forward / inverse / fixed kernel configuration), 3 real z lines in (R2C),
                              * 4 real z lines out (C2R), 5 real strided lines in (R2C) */
@@ -405,7 +425,9 @@ typedef struct dfft_chain_step {
     int32_t tables;         /* DFFT_FORWARD / DFFT_INVERSE: the direction whose dfft_get_pipeline_tables the step's exchange uses -- the
                              * chain's own, except in the chain of dfft_exec_spectral_op: forward up to its "xx" step, inverse from it on */
 } dfft_chain_step;
-/* the steps of the chain the next exec in `direction` (DFFT_SPECTRAL_OP with dims = 3: dfft_exec_spectral_op) of `dims` dimensions
+/* the steps of the chain the next exec in `direction` (DFFT_SPECTRAL_OP with dims = 3: dfft_exec_spectral_op; DFFT_SPECTRAL_OPS with dims = 3:
+ * dfft_exec_spectral_ops with as many outputs as option "spectral_outputs" says, empty while that is 1 -- fewer outputs run its first
+ * 2 + 3 nout steps, and the step at position 2 + 3 j + {0, 1, 2} belongs to output j) of `dims` dimensions
  * (1, 2: exec_dim's partial transforms; 3: the whole transform) would run, as options read at exec time choose it; *count receives the number of steps, at most `capacity` are written */
 int dfft_debug_get_chain(const dfft_plan *plan, int direction, int dims, dfft_chain_step *steps, int capacity, int *count);
 /* One operation of the stream and event schedule of an exec (dfft_debug_trace_chain), in the order the exec issues them.  The executor

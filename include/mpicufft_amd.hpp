@@ -222,6 +222,13 @@ public:
     // passes are a single kernel with the multiplier between them (dfft_exec_spectral_op in dfft_c.h: an array in the spectrum's layout,
     // three real 1-D tables (their sum or its reciprocal), or three complex 1-D factor tables cx, cy, cz, alone or times / over that sum).  setOption("spectral_op", 1) before initFFT; `in` is only read; no timer sections.
     void execSpectralOp(void *out, const void *in, const dfft_spectral_op &op) { if (plan_) check(dfft_exec_spectral_op(plan_, out, in, &op)); }
+    // several operators on one input with one forward half: outs[j] = IFFT(ops[j] * FFT(in)), each bit for bit what execSpectralOp gives
+    // (dfft_exec_spectral_ops).  setOption("spectral_outputs", K) with K >= nout next to "spectral_op", before initFFT; the outputs and
+    // `in` are all different buffers.
+    void execSpectralOps(void *const *outs, const void *in, const dfft_spectral_op *ops, int nout)
+    {
+        if (plan_) check(dfft_exec_spectral_ops(plan_, nout, outs, in, ops));
+    }
     // extension (no counterpart in the reference): buffers on the physical backing this plan's passes run fastest on, see
     // dfft_tune_placement in dfft_c.h; free them with dfft_free.  Collective on a multi-rank plan.
     void tunePlacement(const void *in, int tries, void **out, void **back = nullptr)

@@ -9,7 +9,11 @@
 The paths alternate within one process (a, b, c, d, a, b, c, d, ...): warm-ups first, then --reps repetitions each, every path bracketed by
 device events on the stream the plan runs on.  One rank, R2C; shapes N^3 for --sizes, both precisions, both spectral_layout settings.
 Prints one line per configuration and, with --out, appends them to a file.  The spread of (a) over repeated runs of the tool is the
-yardstick for the ratios: run it more than once (--label names the run in the output)."""
+yardstick for the ratios: run it more than once (--label names the run in the output).
+
+--outputs K (2 .. 8) times something else: ONE execSpectralOps with K kind-5 operators (components of the gradient of a Poisson solution:
+factor table i * k_d over the sums -|k|^2) against K calls of execSpectralOp with the same operators, on the same plan and buffers, the
+two alternating in one process.  It prints both times, their ratio and the ratio the trip counts predict, (4 + 6 K) / (10 K)."""
 import argparse
 import os
 import statistics
@@ -72,6 +76,51 @@ def measure(n, prec, layout, reps, warmup):
     return {p: (statistics.median(v), min(v), max(v)) for p, v in times.items()}
 
 
+def measure_outputs(n, prec, layout, K, reps, warmup):
+    """(multi, singles): median, min, max in ms of one execSpectralOps with K operators and of K execSpectralOp calls"""
+    cdt, rdt = (torch.complex128, torch.float64) if prec == "double" else (torch.complex64, torch.float32)
+    esz = 16 if prec == "double" else 8
+    pl = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), None, precision=prec)
+    pl.setOption("spectral_op", 1 if n & (n - 1) == 0 else 2)
+    pl.setOption("spectral_outputs", K)
+    pl.setOption("spectral_layout", layout)
+    pl.initFFT(dfft.GlobalSize(n, n, n), dfft.Pencil_Partition(1, 1), True)
+    stream = torch.cuda.current_stream()
+    pl.setStream(stream.cuda_stream)
+    nreal = n * n * n
+    bufs = [dfft.DeviceBuffer.alloc(nreal * esz // 2) for _ in range(1 + K)]
+    u, outs = bufs[0].tensor(rdt), [b.tensor(rdt) for b in bufs[1:]]
+    g = torch.Generator(device="cuda").manual_seed(7)
+    u.copy_(torch.rand(nreal, generator=g, device="cuda", dtype=rdt) * 255 - 127.5)
+    kx, ky, kz = (torch.from_numpy(k).cuda() for k in pl.wavenumbers())
+    sums = tuple(-(k.to(rdt) ** 2) for k in (kx, ky, kz))
+    ops = []
+    for j in range(K):
+        factors = [None, None, None]
+        factors[j % 3] = (1j * (kx, ky, kz)[j % 3].to(rdt)).to(cdt)
+        ops.append(dict(factors=tuple(factors), tables=sums, reciprocal=True, scale=1.0 / nreal))
+
+    def singles():
+        for out, op in zip(outs, ops):
+            pl.execSpectralOp(out, u, **op)
+
+    paths = {"multi": lambda: pl.execSpectralOps(outs, u, ops), "singles": singles}
+    times = {p: [] for p in paths}
+    for it in range(warmup + reps):
+        for name, fn in paths.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            fn()
+            b.record(stream)
+            b.synchronize()
+            if it >= warmup:
+                times[name].append(a.elapsed_time(b))
+    del u, outs
+    for b in bufs:
+        b.free()
+    return {p: (statistics.median(v), min(v), max(v)) for p, v in times.items()}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", type=int, nargs="+", default=[512, 1024])
@@ -79,15 +128,29 @@ def main():
     ap.add_argument("--layouts", type=int, nargs="+", default=[0, 1], choices=[0, 1])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--outputs", type=int, default=0, metavar="K",
+                    help="time one execSpectralOps with K operators against K calls of execSpectralOp instead of the paths (a) .. (d)")
     ap.add_argument("--label", default="")
     ap.add_argument("--out", default=None, help="append the result lines to this file")
     args = ap.parse_args()
     if args.reps < 20:
         ap.error("--reps must be at least 20")
+    if args.outputs and not 2 <= args.outputs <= 8:
+        ap.error("--outputs must be 2 .. 8")
     lines = []
     for n in args.sizes:
         for prec in args.precisions:
             for layout in args.layouts:
+                if args.outputs:
+                    K = args.outputs
+                    t = measure_outputs(n, prec, layout, K, args.reps, args.warmup)
+                    line = (f"{args.label + ' ' if args.label else ''}{n}^3 R2C {prec:<6s} spectral_layout={layout}  outputs={K}  reps={args.reps}  ms median (min .. max):  "
+                            + "  ".join(f"{name} {t[p][0]:8.3f} ({t[p][1]:.3f} .. {t[p][2]:.3f})" for p, name in
+                                        (("multi", "one execSpectralOps"), ("singles", f"{K} x execSpectralOp")))
+                            + f"   multi/singles = {t['multi'][0] / t['singles'][0]:.3f} (trips {4 + 6 * K}/{10 * K} = {(4 + 6 * K) / (10 * K):.3f})")
+                    print(line, flush=True)
+                    lines.append(line)
+                    continue
                 t = measure(n, prec, layout, args.reps, args.warmup)
                 a = t["a"][0]
                 line = (f"{args.label + ' ' if args.label else ''}{n}^3 R2C {prec:<6s} spectral_layout={layout}  reps={args.reps}  ms median (min .. max):  "
