@@ -21,25 +21,14 @@ import distributedfft_amd as dfft
 from distributedfft_amd import api
 from distributedfft_amd._lib import SpectralOp
 
+import host_check
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_factor_forms_emulated_on_the_host(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    src = os.path.join(os.path.dirname(__file__), "cpp", "spectral_factor_check.hip")
-    builds = []
-    for tag, flag in (("f64", []), ("f32", ["-DCHAIN_F32"])):
-        exe = str(tmp_path / ("spectral_factor_check_" + tag))
-        builds.append((exe, subprocess.Popen([hipcc, "-O1", "-std=c++17", "--offload-arch=gfx950", "-fno-slp-vectorize", *flag, src, "-o", exe])))
-    runs = []
-    for exe, proc in builds:
-        assert proc.wait() == 0
-        runs.append(subprocess.Popen([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    for r in runs:
-        out = r.communicate()[0]
-        assert r.returncode == 0 and "33 forms of 11 configurations checked, 0 failed" in out and "ALL OK" in out, out[-2000:]
+    for out in host_check.run(tmp_path, "spectral_factor_check.hip", (("f64", []), ("f32", ["-DCHAIN_F32"]))).values():
+        assert "33 forms of 11 configurations checked, 0 failed" in out and "ALL OK" in out, out[-2000:]
 
 
 # ---- wavenumbers() ------------------------------------------------------------------------------------------------------------------

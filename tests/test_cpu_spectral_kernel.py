@@ -5,26 +5,9 @@ Three forms per configuration: the array multiplier, and the table forms w[sigma
 f = scale / sum (0 at a zero sum), sum = tx[t + NT * sigma(c)] + sy + sz from integer tables that contain zero sums.  A failure of
 tests/test_gpu_spectral_op.py::test_table_multiplier_against_numpy with this test green points at the plan's table offsets (Launch::ty_off,
 the rank's slices of ay and az), not at the kernel's hand-off."""
-import os
-import shutil
-import subprocess
-
-import pytest
+import host_check
 
 
 def test_forward_multiply_inverse_chain_emulated_on_the_host(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    src = os.path.join(os.path.dirname(__file__), "cpp", "spectral_chain_check.hip")
-    builds = []
-    for tag, flag in (("f64", []), ("f32", ["-DCHAIN_F32"])):
-        exe = str(tmp_path / ("spectral_chain_check_" + tag))
-        builds.append((exe, subprocess.Popen([hipcc, "-O1", "-std=c++17", "--offload-arch=gfx950", "-fno-slp-vectorize", *flag, src, "-o", exe])))
-    runs = []
-    for exe, proc in builds:
-        assert proc.wait() == 0
-        runs.append(subprocess.Popen([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    for r in runs:
-        out = r.communicate()[0]
-        assert r.returncode == 0 and "33 forms of 11 configurations checked, 0 failed" in out and "ALL OK" in out, out[-2000:]
+    for out in host_check.run(tmp_path, "spectral_chain_check.hip", (("f64", []), ("f32", ["-DCHAIN_F32"]))).values():
+        assert "33 forms of 11 configurations checked, 0 failed" in out and "ALL OK" in out, out[-2000:]

@@ -7,41 +7,25 @@ spectral_factor_point / spectral_factor_line.  The hand-off walks the registers 
 registers that start as NaN: with the chunk width the powers of two had, 4, the configurations with E = 10, 18, 30, 50 fail here.  The number of configurations checked is held to the number of mixed-radix lengths
 dfft.spectral_op_supported reports: a length the library accepts and the emulation never saw cannot pass.
 The translation unit is compiled in parts, all at once (host side only; about a minute of wall time on eight cores for both precisions)."""
-import os
 import re
-import shutil
-import subprocess
-
-import pytest
 
 import distributedfft_amd as dfft
+
+import host_check
 
 PARTS = 4
 
 
 def test_mixed_radix_chain_emulated_on_the_host(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    src = os.path.join(os.path.dirname(__file__), "cpp", "spectral_mixed_chain_check.hip")
-    builds = []
-    for prec, flag in (("double", []), ("float", ["-DCHAIN_F32"])):
-        for k in range(PARTS):
-            exe = str(tmp_path / f"spectral_mixed_chain_check_{prec}_{k}")
-            cmd = [hipcc, "-O1", "-std=c++17", "--offload-arch=gfx950", "--cuda-host-only", "-fno-slp-vectorize", *flag,
-                   f"-DCHECK_PARTS={PARTS}", f"-DCHECK_PART={k}", src, "-o", exe]
-            builds.append((prec, exe, subprocess.Popen(cmd)))
-    runs = []
-    for prec, exe, proc in builds:
-        assert proc.wait() == 0
-        runs.append((prec, subprocess.Popen([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
+    variants = [(f"{prec}_{k}", [*flag, f"-DCHECK_PARTS={PARTS}", f"-DCHECK_PART={k}"])
+                for prec, flag in (("double", []), ("float", ["-DCHAIN_F32"])) for k in range(PARTS)]
+    outputs = host_check.run(tmp_path, "spectral_mixed_chain_check.hip", variants, [*host_check.FLAGS, "--cuda-host-only"])
     counted = {"double": 0, "float": 0}
-    for prec, r in runs:
-        out = r.communicate()[0]
+    for tag, out in outputs.items():
         m = re.search(r"(\d+) forms of (\d+) configurations checked, (\d+) failed", out)
-        assert r.returncode == 0 and m and "ALL OK" in out, out[-2000:]
+        assert m and "ALL OK" in out, out[-2000:]
         assert int(m.group(1)) == 6 * int(m.group(2)) and int(m.group(3)) == 0, out[-2000:]
-        counted[prec] += int(m.group(2))
+        counted[tag.split("_")[0]] += int(m.group(2))
     for prec in counted:
         mixed = [n for n in range(2, 2049) if n & (n - 1) and dfft.spectral_op_supported(n, prec, 2)]
         assert counted[prec] == len(mixed) > 40, (prec, counted[prec], mixed)
