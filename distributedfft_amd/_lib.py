@@ -83,6 +83,7 @@ SYMBOLS = [
     ("dfft_exec_dim", _i, [_vp, _vp, _vp, _i, _i]),
     ("dfft_exec_spectral_op", _i, [_vp, _vp, _vp, C.POINTER(SpectralOp)]),
     ("dfft_exec_spectral_ops", _i, [_vp, _i, C.POINTER(_vp), _vp, C.POINTER(SpectralOp)]),
+    ("dfft_exec_spectral_sum", _i, [_vp, _vp, _i, C.POINTER(_vp), C.POINTER(SpectralOp)]),
     ("dfft_spectral_op_supported", _i, [_i, _sz, _i]),
     ("dfft_get_in_size", _i, [_vp, _psz]),
     ("dfft_get_in_start", _i, [_vp, _psz]),

@@ -24,6 +24,7 @@ Sync, Streams, MPI_Type = 0, 1, 2
 FORWARD, INVERSE = -1, 1
 SPECTRAL_OP = 2      # DFFT_SPECTRAL_OP: the chain of execSpectralOp in debugChain / debugTrace
 SPECTRAL_OPS = 3     # DFFT_SPECTRAL_OPS: the chain of execSpectralOps for as many outputs as option spectral_outputs says
+SPECTRAL_SUM = 4     # DFFT_SPECTRAL_SUM: the chain of execSpectralSum for as many inputs as option spectral_inputs says
 
 
 class GlobalSize:
@@ -408,6 +409,27 @@ class MPIcuFFT:
                                                                     op.get("scale", 1.0), op.get("factors")) for op in ops])
         c_outs = (C.c_void_p * max(1, len(outs)))(*[_ptr(o).value for o in outs])
         check(lib().dfft_exec_spectral_ops(self._h, len(outs), c_outs, _ptr(in_), c_ops))
+
+    def execSpectralSum(self, out, ins, ops):
+        """out = sum_j IFFT(m_j * FFT(ins[j])), unnormalised, with one inverse half for all inputs: per input the z and y passes, the
+        forward exchanges and the fused x kernel run, which from the second input on adds its result to the first's in the order
+        j = 0, 1, ... (one rounding per addition); the inverse y and z passes run once (dfft_exec_spectral_sum) -- the divergence of a
+        vector field, a component of a curl.  The plan needs setOption("spectral_inputs", K) with K >= len(ins) next to spectral_op,
+        before initFFT.  ops: one dict per input with the keywords of execSpectralOp (tables, reciprocal, scale, factors; an array
+        multiplier= is refused by the library: the sum takes the table forms).  out and every ins[j] are blocks of the input layout;
+        the inputs are only read and out is none of them.  With one input the result is bit for bit execSpectralOp's."""
+        from ._lib import SpectralOp
+        ins, ops = list(ins), list(ops)
+        if len(ins) != len(ops):
+            raise DfftError("execSpectralSum takes one operator per input")
+        for op in ops:
+            extra = set(op) - {"multiplier", "tables", "reciprocal", "scale", "factors"}
+            if extra:
+                raise DfftError(f"execSpectralSum: unknown operator keyword {sorted(extra)[0]}")
+        c_ops = (SpectralOp * max(1, len(ops)))(*[self._spectral_op(op.get("multiplier"), op.get("tables"), op.get("reciprocal", False),
+                                                                    op.get("scale", 1.0), op.get("factors")) for op in ops])
+        c_ins = (C.c_void_p * max(1, len(ins)))(*[_ptr(u).value for u in ins])
+        check(lib().dfft_exec_spectral_sum(self._h, _ptr(out), len(ins), c_ins, c_ops))
 
     @staticmethod
     def _spectral_op(multiplier, tables, reciprocal, scale, factors):

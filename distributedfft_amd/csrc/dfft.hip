@@ -65,14 +65,17 @@ static int launch(dfft_plan *p, const Launch &L, int form, int axis, bool conj, 
 }
 
 // one launch of group xx (fft_spectral_kernel): forward x pass, the multiplier `op`, inverse x pass
-static int launch_spectral(dfft_plan *p, const Launch &L, const dfft_spectral_op &op, const char *in, char *out, hipStream_t stream)
+// (acc: added to what `out` holds -- the accumulating instantiations: table forms and STORE_TILED_SAME only, checked here and nowhere
+// below, the kernel libraries' launchers take both for granted)
+static int launch_spectral(dfft_plan *p, const Launch &L, const dfft_spectral_op &op, bool acc, const char *in, char *out, hipStream_t stream)
 {
     if (L.args.ntiles == 0) return 0;
     const size_t real = p->esz / 2;
     PassArgs A = L.args;
     A.in = in + L.in_off; A.out = out + L.out_off; A.tw = p->ax[2].tw; A.debug = 0;
     fill_tables(p, L, A);
-    A.mkind = op.kind; A.mscale = op.scale;
+    A.mkind = op.kind; A.mscale = op.scale; A.acc = acc ? 1 : 0;
+    if (acc && (op.kind == 0 || A.store_kind != STORE_TILED_SAME)) return fail(ERR_UNSUPPORTED, "spectral_sum: no accumulating kernel for this launch");
     if (op.kind == 0) A.mult = static_cast<const char *>(op.mult) + L.mult_off * p->esz;
     else if (op.kind != 3) { A.mtx = op.ax; A.mty = static_cast<const char *>(op.ay) + L.ty_off * real; A.mtz = op.az; }
     if (op.kind >= 3) {      // the factor tables; cy starts at the chunk's first ky row like ay, in complex elements
@@ -169,6 +172,7 @@ static const Chain &chain_of(const dfft_plan *p, int direction, int dims)
     const Pipeline &pl = p->pl;
     if (direction == DFFT_SPECTRAL_OP) return pl.spec;      // (dfft_exec_spectral_op; empty without option spectral_op)
     if (direction == DFFT_SPECTRAL_OPS) return pl.spec_multi;      // (dfft_exec_spectral_ops; empty while option spectral_outputs is 1)
+    if (direction == DFFT_SPECTRAL_SUM) return pl.spec_sum;        // (dfft_exec_spectral_sum; empty while option spectral_inputs is 1)
     const bool fwd = direction != DFFT_INVERSE;
     if (dims == 3 && one_rank_alternative(p) && !(fwd ? pl.one_fwd : pl.one_inv).steps.empty()) return fwd ? pl.one_fwd : pl.one_inv;
     return fwd ? pl.fwd[dims - 1] : pl.inv[dims - 1];
@@ -258,6 +262,7 @@ struct HipSink {
     }
     char *buf(int b) const
     {
+        if (b <= buf_input(1)) return const_cast<char *>(static_cast<const char *>(p->ins[-b - 9]));      // input j >= 1 of a multi-input chain (buf_input)
         if (b < BUF_IN) return static_cast<char *>(p->outs[-b - 2]);      // output j >= 1 of a multi-output chain (buf_output)
         return b == BUF_IN ? const_cast<char *>(static_cast<const char *>(in)) : b == BUF_OUT ? static_cast<char *>(out)
                                                                                : static_cast<char *>(p->work_d) + (size_t)b * p->domainsize;
@@ -267,7 +272,9 @@ struct HipSink {
         const Step &t = st[(size_t)step];
         const Group &g = p->pl.groups[t.group];
         if (log) log->push_back(trace_launch(p, st, step, chunk, k, s));
-        if (t.group == G_XX) return launch_spectral(p, g.L[(size_t)k], p->ops[spectral_output_of(step)], buf(t.src), buf(t.dst), S[s]);
+        if (t.group == G_XX)
+            return launch_spectral(p, g.L[(size_t)k], p->ops[direction == DFFT_SPECTRAL_SUM ? spectral_input_of(step) : spectral_output_of(step)],
+                                   t.form == FORM_FIXED_ACC, buf(t.src), buf(t.dst), S[s]);
         return launch(p, g.L[(size_t)k], t.form, g.axis, t.conj, buf(t.src), buf(t.dst), S[s]);
     }
     int xchg(int step, int chunk, int s, int ready)
@@ -369,17 +376,18 @@ template <typename Sink> static int schedule_chain(const dfft_plan *p, const Cha
 
 static int trace_slot(int direction)
 {
-    return direction == DFFT_SPECTRAL_OPS ? 3 : direction == DFFT_SPECTRAL_OP ? 2 : direction == DFFT_INVERSE ? 1 : 0;
+    return direction == DFFT_SPECTRAL_SUM ? 4 : direction == DFFT_SPECTRAL_OPS ? 3 : direction == DFFT_SPECTRAL_OP ? 2 : direction == DFFT_INVERSE ? 1 : 0;
 }
 
 // Runs one execution chain: schedule_chain through the sink that issues HIP calls.  `prefix`: the chain to run where it is not
-// chain_of's (the first steps of Pipeline::spec_multi for fewer outputs than the plan was built for)
+// chain_of's (the first steps of Pipeline::spec_multi for fewer outputs than the plan was built for, spectral_sum_chain for fewer inputs)
 static int run_chain(dfft_plan *p, int direction, int dims, void *out, const void *in, const Chain *prefix = nullptr)
 {
     const Chain &ch = prefix ? *prefix : chain_of(p, direction, dims);
     if (ch.steps.empty())
         return direction == DFFT_SPECTRAL_OP ? fail(ERR_STATE, "plan was initialised without option spectral_op")
                : direction == DFFT_SPECTRAL_OPS ? fail(ERR_STATE, "set spectral_outputs before dfft_init")
+               : direction == DFFT_SPECTRAL_SUM ? fail(ERR_STATE, "set spectral_inputs before dfft_init")
                                              : fail(ERR_UNSUPPORTED, "the Y_Then_ZX sequence is forward only (as in the reference)");
     const StreamUse use = streams_of(p, ch);
     p->nspans = 0; p->last_dir = direction == DFFT_INVERSE ? DFFT_INVERSE : DFFT_FORWARD;
@@ -603,6 +611,7 @@ static int *option_slot(Options &o, const std::string &k)
     if (k == "spectral_layout") return &o.spectral;
     if (k == "spectral_op") return &o.spectral_op;
     if (k == "spectral_outputs") return &o.spectral_outputs;
+    if (k == "spectral_inputs") return &o.spectral_inputs;
     if (k == "compute_streams") return &o.compute_streams;
     if (k == "trace") return &o.trace;
     for (int i = 0; i < 6; i++) {
@@ -837,6 +846,14 @@ int dfft_init(dfft_plan *p, size_t Nx, size_t Ny, size_t Nz, int P1, int P2, int
         // the multi-output chain never writes the slice xx reads: one more slice wherever the single-output chain writes it again
         // (every grid but a P1 x P2 pencil: pipeline.hip), whatever the number of outputs
         if (P1 == 1 || P2 == 1) p->worksize_d += p->domainsize;
+    }
+    if (p->opt.spectral_inputs < 1 || p->opt.spectral_inputs > DFFT_SPECTRAL_MAX_INPUTS)
+        return fail(ERR_ARG, "spectral_inputs: 1 to " + std::to_string(DFFT_SPECTRAL_MAX_INPUTS));
+    if (p->opt.spectral_inputs > 1) {
+        if (!p->opt.spectral_op) return fail(ERR_ARG, "spectral_inputs: needs option spectral_op = 1 or 2");
+        // the accumulator of the multi-input chain: one slice above the single chain's on every grid, whatever the number of inputs.  The
+        // multi-output chain's extra slice has the same index and the two chains never run at the same time: a plan pays for it once
+        if (!(p->opt.spectral_outputs > 1 && (P1 == 1 || P2 == 1))) p->worksize_d += p->domainsize;
     }
     // (one rank: the inverse of an x-contiguous spectrum cannot be the forward launches with conjugation -- their input is the natural grid)
     p->spectral_mirror = p->opt.spectral && p->nranks == 1;
@@ -1141,6 +1158,33 @@ int dfft_exec_spectral_ops(dfft_plan *p, int nout, void *const *outs, const void
     return 0;
 }
 
+int dfft_exec_spectral_sum(dfft_plan *p, void *out, int nin, const void *const *ins, const dfft_spectral_op *ops)
+{
+    if (p && p->initialized && p->pl.spec_sum.steps.empty()) return fail(ERR_STATE, "set spectral_inputs before dfft_init");
+    TRY(check_ready(p));
+    if (nin < 1 || nin > p->opt.spectral_inputs)
+        return fail(ERR_ARG, "spectral_sum: nin must be 1 to " + std::to_string(p->opt.spectral_inputs) + " (option spectral_inputs)");
+    if (!out || !ins || !ops) return fail(ERR_ARG, "null buffer or operator");
+    for (int j = 0; j < nin; j++) {
+        if (!ins[j]) return fail(ERR_ARG, "null buffer or operator");
+        if (ins[j] == out) return fail(ERR_ARG, "spectral_sum: out == ins[" + std::to_string(j) + "] is not supported");
+    }
+    dfft_spectral_op taken[DFFT_SPECTRAL_MAX_INPUTS];
+    for (int j = 0; j < nin; j++) {
+        const std::string which = " ops[" + std::to_string(j) + "]";
+        TRY(take_spectral_op(p, &ops[j], which, taken[j]));
+        // K domain-sized multiplier arrays, the 11-trip form: the accumulating kernels exist for the table forms alone
+        if (taken[j].kind == 0)
+            return fail(ERR_UNSUPPORTED, "spectral_op" + which + ": kind 0 (array) is not supported, the sum takes the table forms, kinds 1-5");
+    }
+    for (int j = 0; j < nin; j++) { p->ops[j] = taken[j]; p->ins[j] = ins[j]; }
+    // exchange 2 backwards follows the last xx, so fewer inputs are not a prefix of the plan's chain; the slices do not depend on nin
+    const Chain ch = nin == p->opt.spectral_inputs ? p->pl.spec_sum : spectral_sum_chain(p, nin);
+    TRY(run_chain(p, DFFT_SPECTRAL_SUM, 3, out, ins[0], &ch));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
 int dfft_get_in_size(const dfft_plan *p, size_t s[3])
 {
     if (!p || !p->initialized) return fail(ERR_STATE, "plan not initialised");
@@ -1262,7 +1306,7 @@ int dfft_debug_get_pass(const dfft_plan *p, const char *name, int index, dfft_pa
 int dfft_debug_get_chain(const dfft_plan *p, int direction, int dims, dfft_chain_step *steps, int capacity, int *count)
 {
     if (!p || !p->initialized) return fail(ERR_STATE, "plan not initialised");
-    const bool spec = (direction == DFFT_SPECTRAL_OP || direction == DFFT_SPECTRAL_OPS) && dims == 3;
+    const bool spec = (direction == DFFT_SPECTRAL_OP || direction == DFFT_SPECTRAL_OPS || direction == DFFT_SPECTRAL_SUM) && dims == 3;
     if (dims < 1 || dims > 3 || (direction != DFFT_FORWARD && direction != DFFT_INVERSE && !spec)) return fail(ERR_ARG, "bad direction or dims");
     const Chain &ch = chain_of(p, direction, dims);
     const std::vector<Step> &st = ch.steps;
@@ -1283,7 +1327,7 @@ int dfft_debug_get_chain(const dfft_plan *p, int direction, int dims, dfft_chain
 int dfft_debug_trace_chain(const dfft_plan *p, int direction, int dims, dfft_trace_op *ops, int capacity, int *count)
 {
     if (!p || !p->initialized) return fail(ERR_STATE, "plan not initialised");
-    const bool spec = (direction == DFFT_SPECTRAL_OP || direction == DFFT_SPECTRAL_OPS) && (dims == 3 || dims == 0);
+    const bool spec = (direction == DFFT_SPECTRAL_OP || direction == DFFT_SPECTRAL_OPS || direction == DFFT_SPECTRAL_SUM) && (dims == 3 || dims == 0);
     if (dims < 0 || dims > 3 || (direction != DFFT_FORWARD && direction != DFFT_INVERSE && !spec)) return fail(ERR_ARG, "bad direction or dims");
     std::vector<dfft_trace_op> dry;
     if (dims > 0) {

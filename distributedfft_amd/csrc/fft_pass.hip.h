@@ -134,11 +134,14 @@ struct PassArgs {
     uint64_t MK, MA, ME;
     const void *mtx, *mty, *mtz;
     const void *mcx, *mcy, *mcz;
+    // fft_spectral_kernel only: 1 = add the result to what `out` holds (the ACC = 1 instantiations: table forms, STORE_TILED_SAME).  Like swap,
+    // set by the executor per step, not part of a launch descriptor
+    int32_t acc;
 };
 // PassArgs and PassInfo (dfft_internal.hpp) cross the seam between libdfft_amd.so and libdfft_amd_any.so by pointer (any_loader.hip ->
 // any_exports.hip).  Bump this by hand whenever either struct changes: the loader refuses a library built with another value, or with
 // other sizes of the two structs.
-#define DFFT_PASS_ABI 2
+#define DFFT_PASS_ABI 3
 
 // ------------------------------------------------------------------------------------------
 // complex number = native 2-vector.  For fp32 that is the point: a <2 x float> lives in an aligned register pair and its
@@ -1168,11 +1171,79 @@ template <typename Cfg> constexpr int spectral_chunk()
     return E < 8 ? E : E % 4 == 0 ? 4 : E % 6 == 0 ? 6 : E % 5 == 0 ? 5 : E % 3 == 0 ? 3 : 2;
 }
 
+// The load twin of store_tile's STORE_TILED_SAME forms, for the accumulating store of fft_spectral_kernel<.., ACC = 1>: old[c - C0] = what
+// `out` holds where store_tile<Cfg, C0, C1> stores register c.  The four branches are store_tile's, condition for condition and address for
+// address (uniform table, per-lane table, one block with a scalar base, generic segments), so that a launch reads exactly the addresses it
+// writes.  Plain loads: the launch before has just written these values.  A lane without a line gets zeros (store_tile stores nothing there).
+template <typename Cfg, int C0, int C1>
+__device__ __forceinline__ void load_stored_tile(const PassArgs &A, const typename Cfg::C *out, const TilePos<Cfg::kTL> &P,
+                                                 int t2, typename Cfg::C *old)
+{
+    using C = typename Cfg::C;
+    using R = typename Cfg::real;
+    constexpr int N = Cfg::kN, E = Cfg::kE, TL = Cfg::kTL, NT = Cfg::NT;
+    constexpr int RL = Cfg::RLAST;
+    constexpr int S = E / RL;
+    static_assert(Cfg::kFIX == 0, "the generic address forms");
+    if (!P.ok) {
+        static_for<C0, C1>([&](auto cc) { constexpr int c = decltype(cc)::value; old[c - C0].x = (R)0; old[c - C0].y = (R)0; });
+        return;
+    }
+    const uint32_t a2 = P.a, b2 = P.b, tws = P.tw;
+    const int l2 = P.l;
+    const uint64_t sk = A.SK ? A.SK : (uint64_t)A.LB * A.LA, sb = A.SB ? A.SB : (uint64_t)TL * A.LA;
+    if (Cfg::UNI_STORE_SAME && A.stab && A.suni) {
+        const int t0 = __builtin_amdgcn_readfirstlane(t2);
+        const uint32_t dt = (uint32_t)(t2 - t0);
+        const SegEntry *tab = A.stab + t0;
+        const C *pl = out + ((uint64_t)b2 * sb + (uint64_t)a2 * tws + l2 + (uint64_t)dt * sk);
+        static_for<C0, C1>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            constexpr int k0 = NT * (c % S) + brev(c / S, RL) * (N / RL);
+            const SegEntry e = seg_entry_uniform(tab + k0);
+            old[c - C0] = pl[e.base];
+        });
+    } else if (A.stab) {
+        const uint64_t fixed = (uint64_t)b2 * sb + (uint64_t)a2 * tws + l2;
+        static_for<C0, C1>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            constexpr int k0 = NT * (c % S) + brev(c / S, RL) * (N / RL);
+            const SegEntry e = seg_entry(A.stab + (t2 + k0));
+            old[c - C0] = out[e.base + fixed];
+        });
+    } else if (Cfg::kG == 1 && Cfg::kSUB == 1 && A.snseg == 1 && !A.shift && !(A.debug & 2) && !A.addr64 &&
+               ((uint64_t)NT * sk + TL) * sizeof(C) < (1ull << 32)) {
+        const uint32_t au = (uint32_t)__builtin_amdgcn_readfirstlane((int)a2), bu = (uint32_t)__builtin_amdgcn_readfirstlane((int)b2);
+        const uint32_t twu = (uint32_t)__builtin_amdgcn_readfirstlane((int)tws);
+        const char *ub = reinterpret_cast<const char *>(out + (A.sseg->base[0] + (uint64_t)bu * sb + (uint64_t)au * twu - (uint64_t)A.sseg->start[0] * sk));
+        const uint32_t lane = (uint32_t)(((uint64_t)t2 * sk + (uint32_t)l2) * sizeof(C));
+        static_for<C0, C1>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            constexpr int k0 = NT * (c % S) + brev(c / S, RL) * (N / RL);
+            old[c - C0] = *reinterpret_cast<const C *>(ub + (uint64_t)k0 * sk * sizeof(C) + lane);
+        });
+    } else {
+        static_for<C0, C1>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            constexpr int k0 = NT * (c % S) + brev(c / S, RL) * (N / RL);
+            const uint32_t k = t2 + k0;
+            uint32_t s0 = A.sseg->start[0];
+            uint64_t bs = A.sseg->base[0];
+            for (int s = 1; s < A.snseg; s++)
+                if (k >= A.sseg->start[s]) { s0 = A.sseg->start[s]; bs = A.sseg->base[s]; }
+            old[c - C0] = out[bs + (uint64_t)(k - s0) * sk + (uint64_t)b2 * sb + (uint64_t)a2 * tws + l2];
+        });
+    }
+}
+
 // TABLES: 0 = the multiplier is a complex array (PassArgs::mkind 0), 1 = it is built from three real tables (mkind 1, 2), 2 = from three
 // complex tables, with or without the real ones (mkind 3, 4, 5).  Separate instantiations, not a branch: with the array and the table form
 // in one kernel the transformed registers flow through either and the 1024-point fp64 configuration takes 152 VGPRs instead of 128, the
 // 2048-point one spills.  (mkind is uniform over the launch: the branches on it inside TABLES == 2 are scalar.)
-template <typename Cfg, int TABLES>
+// ACC = 1 (PassArgs::acc; dfft_exec_spectral_sum, inputs j >= 1): the result is ADDED to what `out` holds, out[p] = out[p] + w.  Every point
+// of a tile is stored by one lane of one workgroup, so the read-modify-write needs neither atomics nor a barrier.  A compile-time
+// parameter for the reason above: the plain kernels (ACC = 0) contain none of it.  The launch must be STORE_TILED_SAME.
+template <typename Cfg, int TABLES, int ACC = 0>
 __global__ __launch_bounds__(Cfg::THREADS, spectral_waves<Cfg>()) void fft_spectral_kernel(const PassArgs A)
 {
     using C = typename Cfg::C;
@@ -1294,7 +1365,32 @@ __global__ __launch_bounds__(Cfg::THREADS, spectral_waves<Cfg>()) void fft_spect
     static_for<0, E>([&](auto cc) { constexpr int c = decltype(cc)::value; w[c].y = -w[c].y; });
     int t4 = t3, lw4 = lw3;      // (and the store's addresses are worked out after the second chain, not before it)
     asm volatile("" : "+v"(t4), "+v"(lw4));
-    store_tile<Cfg>(A, out, tile_pos<Cfg>(A, blk, lw4), t4, w);
+    if constexpr (!ACC) {
+        store_tile<Cfg>(A, out, tile_pos<Cfg>(A, blk, lw4), t4, w);
+    } else {
+        // CH registers at a time, as the multiplier loop: the chunk's old values are all requested before the first of them is added, and
+        // the chunk is stored before the next one's loads are issued (all E loads at once would need E more complex registers; one load
+        // and store per register would pay the latency E times)
+        // The whole term is complete here, in one block, before the store's branches and chunks begin: left to itself the compiler moves
+        // the last butterflies of a chunk down to that chunk, away from the multiplies they were contracted with in the plain kernel,
+        // and the term differs from the plain kernel's in its last bits.  With this t_j has been bit for bit what ACC = 0 stores at
+        // every length compared so far (the zero-input and order tests of tests/test_gpu_spectral_sum.py); the language promises no
+        // such thing, so those tests are what holds a new compiler to it, and only the last bits of a sum depend on it.
+        // out = old + t_j below is one IEEE addition (no multiply is contracted into it either)
+        static_for<0, E>([&](auto cc) { settle(w[decltype(cc)::value]); });
+        const TilePos<Cfg::kTL> P4 = tile_pos<Cfg>(A, blk, lw4);
+        static_for<0, E / CH>([&](auto qq) {
+            constexpr int q = decltype(qq)::value;
+            C old[CH];
+            load_stored_tile<Cfg, q * CH, (q + 1) * CH>(A, out, P4, t4, old);
+            static_for<0, CH>([&](auto jj) {
+                constexpr int j = decltype(jj)::value, c = q * CH + j;
+                w[c].x = old[j].x + w[c].x; w[c].y = old[j].y + w[c].y;
+                settle(w[c]);
+            });
+            store_tile<Cfg, q * CH, (q + 1) * CH>(A, out, P4, t4, w);
+        });
+    }
 }
 
 // ------------------------------------------------------------------------------------------

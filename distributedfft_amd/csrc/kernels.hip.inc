@@ -39,26 +39,32 @@ template <typename Cfg> static int launch_cfg(const PassArgs &A, hipStream_t str
 
 // fft_spectral_kernel (forward transform, pointwise multiplier, inverse transform of complete x lines in one launch): whole tiles,
 // one workgroup per G tiles, the dynamic-LDS attribute as for launch_cfg.  TABLES = the part of spectral_<p>.hip (-DDFFT_PART):
-// 0 array multiplier, 1 real table multipliers, 2 complex factor tables
-template <typename Cfg, int TABLES> static int launch_spectral_cfg(const PassArgs &A, hipStream_t stream)
+// 0 array multiplier, 1 real table multipliers, 2 complex factor tables.  ACC = 1: the accumulating store (PassArgs::acc; parts 3 and 4 =
+// TABLES 1 and 2; STORE_TILED_SAME is the one store kind that has a load twin, which the host engine's launch_spectral checks)
+template <typename Cfg, int TABLES, int ACC = 0> static int launch_spectral_cfg(const PassArgs &A, hipStream_t stream)
 {
+    static_assert(!ACC || TABLES != 0, "the array form has no accumulating instantiation");
     static bool attr_set = false;
     if (!attr_set && Cfg::LDS_BYTES > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&fft_spectral_kernel<Cfg, TABLES>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&fft_spectral_kernel<Cfg, TABLES, ACC>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
     const uint32_t grid = (A.ntiles + Cfg::kG - 1) / Cfg::kG;
     if (grid == 0) return 0;
-    hipLaunchKernelGGL((fft_spectral_kernel<Cfg, TABLES>), dim3(grid), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, A);
+    hipLaunchKernelGGL((fft_spectral_kernel<Cfg, TABLES, ACC>), dim3(grid), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, A);
     return (int)hipGetLastError();
 }
-// (spectral_mixed_<p>.hip has several parts per multiplier form and sets DFFT_SPECTRAL_TABLES itself)
+// (spectral_mixed_<p>.hip has several parts per multiplier form and sets DFFT_SPECTRAL_TABLES itself; the accumulating parts of either
+// family set both)
 #ifndef DFFT_SPECTRAL_TABLES
 #define DFFT_SPECTRAL_TABLES DFFT_PART
 #endif
-#define DFFT_CASE_SPECTRAL(n, v, cfg) case n: return launch_spectral_cfg<cfg, DFFT_SPECTRAL_TABLES>(A, stream);
+#ifndef DFFT_SPECTRAL_ACC
+#define DFFT_SPECTRAL_ACC 0
+#endif
+#define DFFT_CASE_SPECTRAL(n, v, cfg) case n: return launch_spectral_cfg<cfg, DFFT_SPECTRAL_TABLES, DFFT_SPECTRAL_ACC>(A, stream);
 #define DFFT_CASE_SPECTRAL_OK(n, v, cfg) case n: return true;
 
 // MODE 1 = R2C (ONEPLANE: 0 two-plane split through LDS, 1 one-plane split, 2 split in registers with the conjugate-pair

@@ -61,7 +61,7 @@ static std::vector<Launch> &group(Pipeline &pl, int g, size_t n)
 static void clear(Pipeline &pl)
 {
     for (auto &g : pl.groups) g.L.clear();
-    for (Chain *c : {&pl.fwd[0], &pl.fwd[1], &pl.fwd[2], &pl.inv[0], &pl.inv[1], &pl.inv[2], &pl.one_fwd, &pl.one_inv, &pl.spec, &pl.spec_multi}) *c = Chain();
+    for (Chain *c : {&pl.fwd[0], &pl.fwd[1], &pl.fwd[2], &pl.inv[0], &pl.inv[1], &pl.inv[2], &pl.one_fwd, &pl.one_inv, &pl.spec, &pl.spec_multi, &pl.spec_sum}) *c = Chain();
     pl.single = false;
 }
 
@@ -328,6 +328,7 @@ int build_pipeline(dfft_plan *p, Pipeline &pl)
             }
             pl.spec_multi.split = true;
         }
+        if (p->opt.spectral_inputs > 1) pl.spec_sum = spectral_sum_chain(p, p->opt.spectral_inputs);
     }
     // partial transforms: d = 1 stops after the z pass with the natural stage layout [xs][ys][Nzc]; d = 2 after the y pass with
     // [xs][Ny][zs] (z contiguous)
@@ -341,6 +342,45 @@ int build_pipeline(dfft_plan *p, Pipeline &pl)
         pl.one_inv.steps = {{G_FZ, FORM_FWD, BUF_IN, 0, 4, 0, false, 1, true}, {G_FY, FORM_FWD, 0, BUF_IN, 2, 0, true, 1, true},
                             {G_FX, FORM_FWD, BUF_IN, BUF_OUT, 0, 0, true, 1, true}};
     return 0;
+}
+
+// Option spectral_inputs = K >= 2 (dfft_exec_spectral_sum): out = IFFT(sum_j m_j FFT(in_j)) with ONE inverse half -- the chain for
+// nin <= K inputs, 3 nin + 2 steps out of the launch groups of Pipeline::spec:
+//   for j in 0 .. nin - 1:   z: in_j -> E   [ex1: E -> W0]   y: -> ydst   [ex2: -> xsrc]   xx(op j): xsrc -> A
+//   [ex2^-1: A -> isrc]   y^-1: isrc -> idst   [ex1^-1: idst -> zsrc]   z^-1: -> out
+// xx of input 0 stores to A (FORM_FIXED), xx of every later input adds to it (FORM_FIXED_ACC): A = ((t0 + t1) + t2) ...  Exchange 2
+// backwards follows the LAST xx only, so a chain for fewer inputs is not a prefix of a longer one: dfft_exec_spectral_sum builds its
+// own.  The accumulator A has to survive the forward halves of the later inputs, so it is none of the slices they write or receive
+// into (E, W0, ydst, xsrc) -- in every grid class a new slice above those of Pipeline::spec, A = E + 1; the forward slices are spec's:
+//              E  ysrc ydst xsrc  A   isrc idst zsrc
+//   one rank   1   1    0    0    2    2    0    0
+//   slab       2   2    0    1    3    2    1    1
+//   1 x P2     2   0    1    1    3    3    2    1
+//   P1 x P2    3   0    1    2    4    1    3    0
+// After the last xx nothing has to be kept, so the inverse half reuses the forward slices (spec's assignment with A in the place of xd).
+// Ordering: z of input j + 1 writes E and, through y and the exchanges, every forward slice that y and xx of input j still read; it
+// waits for the whole step before it, xx of input j, which itself waited for all of y of input j.  xx of input j + 1 reads and writes A
+// behind that wait and its own (all of y of input j + 1).  tests/test_cpu_spectral_sum.py replays the chain on NaN-filled slices and
+// runs the schedule checker with A counted as read and written by the accumulating launches.
+Chain spectral_sum_chain(const dfft_plan *p, int nin)
+{
+    const int P1 = p->P1, P2 = p->P2;
+    const int x1 = P2 > 1 ? 1 : 0, x2 = P1 > 1 ? 2 : 0;
+    const int zf = p->c2c ? FORM_FWD : FORM_REAL_Z1, zi = p->c2c ? FORM_INV : FORM_REAL_Z2;
+    const int E = (P1 > 1) + (P2 > 1) + 1, A = E + 1;
+    const int ysrc = P2 > 1 ? 0 : E, ydst = P2 > 1 ? 1 : 0, xsrc = P1 > 1 ? ydst + 1 : ydst;
+    const int isrc = P1 > 1 ? (P2 > 1 ? 1 : E) : A, idst = P2 > 1 ? E : (P1 > 1 ? 1 : 0), zsrc = P2 > 1 ? (P1 > 1 ? 0 : 1) : idst;
+    Chain ch;
+    for (int j = 0; j < nin; j++) {
+        const bool last = j == nin - 1;
+        ch.steps.push_back({G_FZ, zf, buf_input(j), E, -1, x1, j > 0, 1, false, DFFT_FORWARD});
+        ch.steps.push_back({G_FY, FORM_FWD, ysrc, ydst, -1, x2, false, 1, false, DFFT_FORWARD});
+        ch.steps.push_back({G_XX, j ? FORM_FIXED_ACC : FORM_FIXED, xsrc, A, -1, last ? x2 : 0, true, 1, false, DFFT_INVERSE});
+    }
+    ch.steps.push_back({G_IY, FORM_INV, isrc, idst, -1, x1, true, 1, false, DFFT_INVERSE});
+    ch.steps.push_back({G_IZ, zi, zsrc, BUF_OUT, -1, 0, P2 == 1, 1, false, DFFT_INVERSE});
+    ch.split = true;
+    return ch;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -85,17 +85,23 @@ struct Group {
 };
 
 // One step of an execution chain: the launches of a group, chunk by chunk, with the exchange after each chunk (run_chain, dfft.hip).
-enum Buffer { BUF_IN = -2, BUF_OUT = -1 };     // and k >= 0: work-area slice k; -(2 + j): output j >= 1 of a multi-output chain
+enum Buffer { BUF_IN = -2, BUF_OUT = -1 };     // and k >= 0: work-area slice k; -(2 + j): output j >= 1 of a multi-output chain;
+                                               // -(9 + j): input j >= 1 of a multi-input chain
 inline int buf_output(int j) { return j == 0 ? BUF_OUT : -(2 + j); }
+inline int buf_input(int j) { return j == 0 ? BUF_IN : -(9 + j); }
+static_assert(-(2 + (DFFT_SPECTRAL_MAX_OUTPUTS - 1)) > -(9 + 1), "the codes of the outputs end above those of the inputs");
 // the output a step of a spectral-operator chain belongs to (Pipeline::spec: always 0; spec_multi: by position)
 inline int spectral_output_of(int step) { return step < 2 ? 0 : (step - 2) / 3; }
+// ... and the input a step of the multi-input chain belongs to (Pipeline::spec_sum: the triples fz, fy, xx come first)
+inline int spectral_input_of(int step) { return step / 3; }
 enum LineForm {
     FORM_FWD,         // complex lines, kernel configuration vfwd[axis]
     FORM_INV,         // complex lines, vinv[axis]
     FORM_FIXED,       // complex lines, configuration 0
     FORM_REAL_Z1,     // real z pass, mode 1 (R2C)
     FORM_REAL_Z2,     // real z pass, mode 2 (C2R)
-    FORM_REAL_LINES   // real strided lines in, Hermitian half out (the y pass of a Y_Then_ZX R2C plan)
+    FORM_REAL_LINES,  // real strided lines in, Hermitian half out (the y pass of a Y_Then_ZX R2C plan)
+    FORM_FIXED_ACC    // FORM_FIXED, the result added to what dst holds (group xx of the multi-input chain: PassArgs::acc)
 };
 struct Step {
     int group;             // GroupId (an index: dfft_init may rebuild the launches)
@@ -128,6 +134,10 @@ struct Pipeline {
     // The step at position 2 + 3 j + {0, 1, 2} belongs to output j (spectral_output_of): its xx runs operator j, its iz writes output
     // j.  The slices do not depend on K, so an exec of nout < K outputs runs the first 2 + 3 nout steps.  Empty when K == 1
     Chain spec_multi;
+    // option spectral_inputs = K >= 2 (dfft_exec_spectral_sum): K forward halves, one inverse half -- K times fz, fy, xx, then iy, iz
+    // (spectral_sum_chain, pipeline.hip).  The step at position 3 j + {0, 1, 2} belongs to input j (spectral_input_of): its fz reads
+    // input j, its xx runs operator j and, for j >= 1, accumulates.  Empty when K == 1
+    Chain spec_sum;
     bool single = false;                       // the z, x, y order is built
     size_t single_work_elems = 0;              // size of the padded L2 buffer
     std::vector<A2A> f1, f2, i2, i1;          // per chunk exchange tables
@@ -170,6 +180,8 @@ struct Options {
                              // work slice for it; 0: nothing of it exists
     int spectral_outputs = 1; // 1 .. 8 (DFFT_SPECTRAL_MAX_OUTPUTS), needs spectral_op: from 2 on the plan also builds Pipeline::spec_multi for
                              // dfft_exec_spectral_ops and, where that chain needs it, one more work slice; 1: nothing of it exists
+    int spectral_inputs = 1; // 1 .. 8 (DFFT_SPECTRAL_MAX_INPUTS), needs spectral_op: from 2 on the plan also builds Pipeline::spec_sum for
+                             // dfft_exec_spectral_sum and one more work slice, the accumulator (shared with spectral_outputs' extra slice)
     int compute_streams = -1; // 2: the pipeline chunks of a pass alternate over two compute streams, so that the drain of chunk c
                              // overlaps the ramp of chunk c + 1 (a chunk launch of 0.1-0.2 ms pays ~20 us of launch / drain / ramp when
                              // the chunks queue up behind each other on one stream).  -1 = by measurement
@@ -218,10 +230,13 @@ struct dfft_plan {
     std::vector<TimedSpan> spans;
     size_t nspans = 0;
     int last_dir = -1;
-    std::vector<dfft_trace_op> trace_log[4];   // option trace: what the last forward / inverse / spectral-operator / multi-output exec issued
+    std::vector<dfft_trace_op> trace_log[5];   // option trace: what the last forward / inverse / spectral-operator / multi-output / multi-input exec issued
     // the spectral-operator exec being enqueued: the multiplier of output j and, for j >= 1, its buffer (output 0 is the exec's `out`)
+    // (dfft_exec_spectral_sum: the multiplier of input j and, for j >= 1, its buffer; input 0 is the exec's `in`)
+    static_assert(DFFT_SPECTRAL_MAX_INPUTS <= DFFT_SPECTRAL_MAX_OUTPUTS, "ops holds one operator per output or input");
     dfft_spectral_op ops[DFFT_SPECTRAL_MAX_OUTPUTS] = {};
     void *outs[DFFT_SPECTRAL_MAX_OUTPUTS] = {};
+    const void *ins[DFFT_SPECTRAL_MAX_INPUTS] = {};
     int spectral_kernel = 0;                   // option spectral_op: the fused x kernel dfft_init found (dfft::SpectralKernel, axis.hpp)
     // hipGraph replay of single-rank execs (launch-bound small grids): one instantiated graph per (operation, in, out)
     struct GraphEntry { int kind; const void *in; void *out; int uses; hipGraphExec_t exec; };
@@ -234,6 +249,8 @@ int build_pipeline(dfft_plan *p, Pipeline &pl);
 int build_pipeline_zyx(dfft_plan *p, Pipeline &pl);
 int build_pipeline_yzx(dfft_plan *p, Pipeline &pl);
 int build_pipeline_single(dfft_plan *p, Pipeline &pl);
+// the multi-input spectral chain for nin inputs (option spectral_inputs; the slices do not depend on nin)
+Chain spectral_sum_chain(const dfft_plan *p, int nin);
 // shared by dfft.hip and tune.hip
 int check_ready(dfft_plan *p);       // 0 when the plan is initialised and has its device state, else an error code
 // a single rank's complex plan may run its one-rank alternative chains (neither mirror_inverse nor an x-contiguous spectrum asks for

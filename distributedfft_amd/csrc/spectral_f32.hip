@@ -1,7 +1,12 @@
 // spectral_f32.hip -- fft_spectral_kernel (fft_pass.hip.h), f32: the fused forward-multiply-inverse x pass of dfft_exec_spectral_op for the
 // power-of-two lengths 2 .. 2048, each with the default (variant 0) configuration of its length.  Compiled in three parts (-DDFFT_PART =
-// 0: the array multiplier and the entry points, 1: the real table multipliers, 2: the complex factor tables, mkind 3 .. 5).
+// 0: the array multiplier and the entry points, 1: the real table multipliers, 2: the complex factor tables, mkind 3 .. 5), and two more
+// for the accumulating store of dfft_exec_spectral_sum (PassArgs::acc): 3 = the kernels of part 1, 4 = those of part 2, with ACC = 1.
 // The mixed-radix x lengths of option spectral_op = 2 are spectral_mixed_f32.hip's, in libdfft_amd_any.so.
+#if DFFT_PART == 3 || DFFT_PART == 4
+#define DFFT_SPECTRAL_TABLES (DFFT_PART - 2)
+#define DFFT_SPECTRAL_ACC 1
+#endif
 #include "cfg_f32.hip.h"
 
 namespace dfft {
@@ -10,6 +15,8 @@ namespace dfft {
 int launch_spectral_f32_p0(int N, const PassArgs &A, hipStream_t stream);
 int launch_spectral_f32_p1(int N, const PassArgs &A, hipStream_t stream);
 int launch_spectral_f32_p2(int N, const PassArgs &A, hipStream_t stream);
+int launch_spectral_f32_p3(int N, const PassArgs &A, hipStream_t stream);
+int launch_spectral_f32_p4(int N, const PassArgs &A, hipStream_t stream);
 #if DFFT_PART == 0
 int launch_spectral_f32_p0(int N, const PassArgs &A, hipStream_t stream)
 {
@@ -18,6 +25,7 @@ int launch_spectral_f32_p0(int N, const PassArgs &A, hipStream_t stream)
 }
 int launch_spectral_f32(int N, const PassArgs &A, hipStream_t stream)
 {
+    if (A.acc) return A.mkind <= 2 ? launch_spectral_f32_p3(N, A, stream) : launch_spectral_f32_p4(N, A, stream);
     return A.mkind == 0 ? launch_spectral_f32_p0(N, A, stream) : A.mkind <= 2 ? launch_spectral_f32_p1(N, A, stream) : launch_spectral_f32_p2(N, A, stream);
 }
 bool spectral_supported_f32(int N)
@@ -37,7 +45,19 @@ int launch_spectral_f32_p2(int N, const PassArgs &A, hipStream_t stream)
     switch (N) { DFFT_F32_SPECTRAL(DFFT_CASE_SPECTRAL) }
     return -1;
 }
+#elif DFFT_PART == 3
+int launch_spectral_f32_p3(int N, const PassArgs &A, hipStream_t stream)
+{
+    switch (N) { DFFT_F32_SPECTRAL(DFFT_CASE_SPECTRAL) }
+    return -1;
+}
+#elif DFFT_PART == 4
+int launch_spectral_f32_p4(int N, const PassArgs &A, hipStream_t stream)
+{
+    switch (N) { DFFT_F32_SPECTRAL(DFFT_CASE_SPECTRAL) }
+    return -1;
+}
 #else
-#error "DFFT_PART must be 0, 1 or 2"
+#error "DFFT_PART must be 0 .. 4"
 #endif
 }  // namespace dfft

@@ -60,6 +60,8 @@ enum dfft_direction { DFFT_FORWARD = -1, DFFT_INVERSE = 1 };
 #define DFFT_SPECTRAL_OP 2
 #define DFFT_SPECTRAL_OPS 3          /* debug "direction": the multi-output chain for the option's value */
 #define DFFT_SPECTRAL_MAX_OUTPUTS 8
+#define DFFT_SPECTRAL_SUM 4          /* debug "direction": the multi-input chain (dfft_exec_spectral_sum) for the option's value */
+#define DFFT_SPECTRAL_MAX_INPUTS 8
 
 /* struct Configurations, include/params.hpp:83-93.  comm/send method enums are accepted and
  * recorded; the device exchange always runs as one grouped all-to-all per exchange. */
@@ -213,6 +215,13 @@ int dfft_get_pipeline_chunks(const dfft_plan *plan);
  *                      (dfft_work_size_device reports it; none on a P1 x P2 pencil with both factors above 1), because that chain never
  *                      overwrites the slice the fused launch reads.  With 1 no size, launch or chain of the plan differs.  Any other
  *                      value, or K >= 2 without "spectral_op": ERR_ARG at dfft_init.
+ *   "spectral_inputs"  1 (default) .. 8 (DFFT_SPECTRAL_MAX_INPUTS), before dfft_init; from 2 on it needs "spectral_op" = 1 or 2.  K >= 2: the
+ *                      plan also builds the chain of dfft_exec_spectral_sum -- per input the z and y passes with their exchanges and
+ *                      the fused x launch with that input's operator, which from the second input on ADDS its result to the first's,
+ *                      then ONE inverse half -- out of the launches it already has.  It costs one more domain-sized slice of the work
+ *                      area on every grid, the accumulator, the same for every K (dfft_work_size_device reports it); a plan that also
+ *                      sets "spectral_outputs" >= 2 pays for one extra slice in total, the two chains share it.  With 1 no size, launch
+ *                      or chain of the plan differs.  Any other value, or K >= 2 without "spectral_op": ERR_ARG at dfft_init.
  *   "graph"            1: a single-rank plan replays the kernel launches of an exec as one hipGraph from the second call
  *                      with the same (operation, in, out) on; 0 (default): plain launches -- measured 6-8 us faster per
  *                      exec on ROCm 7.2 (profiles/r2_graph_latency.txt)
@@ -314,6 +323,22 @@ int dfft_exec_spectral_op(dfft_plan *plan, void *out, const void *in, const dfft
  * output equal to `in`, an ops[j] that dfft_exec_spectral_op would refuse (the message names j; the same checks, the 32-bit lane-offset
  * bound of kind 0 included: ERR_UNSUPPORTED).  Blocking; collective on a multi-rank plan, every rank with the same nout. */
 int dfft_exec_spectral_ops(dfft_plan *plan, int nout, void *const *outs, const void *in, const dfft_spectral_op *ops);
+/* new: several inputs summed into one output, out = sum_j IFFT(ops[j] * FFT(ins[j])) for j < nin, unnormalised like
+ * dfft_exec_spectral_op -- the divergence of a vector field (3 -> 1), a component of a curl (2 -> 1), the pressure right-hand side of a
+ * Navier-Stokes step -- with ONE inverse half: the inverse transform is linear, so the sum is taken in spectral space.  Per input the z
+ * and y passes, both forward exchanges and the fused x launch run; the fused launch of input 0 stores its result t_0 to a work slice, that
+ * of every later input adds to it IN THE ORDER j = 0, 1, ...: ((t_0 + t_1) + t_2) ..., one rounding per addition; then exchange 2
+ * backwards and the inverse y and z passes run once.  7 nin + 3 trips of a domain-sized buffer through memory and 2 nin + 2 exchanges
+ * instead of the 10 nin and 4 nin of nin calls of dfft_exec_spectral_op plus the caller's pointwise sum and nin - 1 temporaries
+ * (DESIGN.md).  With nin = 1 the result is bit for bit that of dfft_exec_spectral_op.  The operators are the table forms, kinds 1 .. 5;
+ * kind 0 (an array) is refused with ERR_UNSUPPORTED: it would take nin domain-sized multiplier arrays and has no accumulating kernel.
+ * The plan needs option "spectral_inputs" >= nin (ERR_STATE while the option is 1: "set spectral_inputs before dfft_init"); nin = 1 is
+ * valid on such a plan.  Every ins[j] and `out` is a block of the input layout; the inputs are only read, and two equal inputs (with
+ * different operators) are allowed.  Footprint: the ins[j], `out` and the dfft_work_size_device() bytes of the work area.  ERR_ARG:
+ * nin < 1 or above the option's value, a null pointer, `out` equal to an input, an ops[j] that dfft_exec_spectral_op would refuse (the
+ * message names ops[j]).  A refused call writes nothing.  Blocking; collective on a multi-rank plan, every rank with the same nin.  No
+ * phase timing and no hipGraph replay for this chain. */
+int dfft_exec_spectral_sum(dfft_plan *plan, void *out, int nin, const void *const *ins, const dfft_spectral_op *ops);
 /* 1 if dfft_init with default options accepts an x length of Nx points under option "spectral_op" = option_value (1 or 2), else 0
  * (also for another option_value or precision).  Host only: no device is touched; loads libdfft_amd_any.so when Nx is not a power of two. */
 int dfft_spectral_op_supported(int precision, size_t Nx, int option_value);
@@ -413,11 +438,13 @@ typedef struct dfft_chain_step {
     char group[8];          /* launch group, as dfft_debug_get_pass names it */
     int32_t axis;           /* 0 z, 1 y, 2 x */
     int32_t launches, per_chunk;
-    int32_t src, dst;       /* -2 the exec's input, -1 its output (output 0 of dfft_exec_spectral_ops; -(2 + j): its output j >= 1), k >= 0
-                             * slice k of the work area (dfft_domain_size bytes each) */
+    int32_t src, dst;       /* -2 the exec's input (input 0 of dfft_exec_spectral_sum; -(9 + j): its input j >= 1), -1 its output (output 0
+                             * of dfft_exec_spectral_ops; -(2 + j): its output j >= 1), k >= 0 slice k of the work area (dfft_domain_size
+                             * bytes each) */
     int32_t conj;           /* 1: launched with conjugation whatever the descriptor's swap says */
     int32_t form;           /* 0 / 1 / 2 complex lines (forward / inverse / fixed kernel configuration), 3 real z lines in (R2C),
-                             * 4 real z lines out (C2R), 5 real strided lines in (R2C) */
+                             * 4 real z lines out (C2R), 5 real strided lines in (R2C), 6 as 2 with the result ADDED to what dst holds
+                             * (the "xx" steps of inputs j >= 1 of dfft_exec_spectral_sum: the launch reads and writes dst) */
     int32_t exchange;       /* 0, or 1 / 2: that exchange after every chunk, dst -> the next step's src, with the tables
                              * dfft_get_pipeline_tables reports for the exec's direction */
     int32_t split;          /* the same for every step of a chain: 1 if its chunks may alternate over two compute streams (option
@@ -427,7 +454,9 @@ typedef struct dfft_chain_step {
 } dfft_chain_step;
 /* the steps of the chain the next exec in `direction` (DFFT_SPECTRAL_OP with dims = 3: dfft_exec_spectral_op; DFFT_SPECTRAL_OPS with dims = 3:
  * dfft_exec_spectral_ops with as many outputs as option "spectral_outputs" says, empty while that is 1 -- fewer outputs run its first
- * 2 + 3 nout steps, and the step at position 2 + 3 j + {0, 1, 2} belongs to output j) of `dims` dimensions
+ * 2 + 3 nout steps, and the step at position 2 + 3 j + {0, 1, 2} belongs to output j; DFFT_SPECTRAL_SUM with dims = 3:
+ * dfft_exec_spectral_sum with as many inputs as option "spectral_inputs" says, empty while that is 1 -- the step at position
+ * 3 j + {0, 1, 2} belongs to input j, and fewer inputs run the chain a plan with that option value has) of `dims` dimensions
  * (1, 2: exec_dim's partial transforms; 3: the whole transform) would run, as options read at exec time choose it; *count receives the number of steps, at most `capacity` are written */
 int dfft_debug_get_chain(const dfft_plan *plan, int direction, int dims, dfft_chain_step *steps, int capacity, int *count);
 /* One operation of the stream and event schedule of an exec (dfft_debug_trace_chain), in the order the exec issues them.  The executor

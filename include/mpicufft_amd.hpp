@@ -229,6 +229,13 @@ public:
     {
         if (plan_) check(dfft_exec_spectral_ops(plan_, nout, outs, in, ops));
     }
+    // several inputs summed into one output with one inverse half: out = sum_j IFFT(ops[j] * FFT(ins[j])), the sum taken in the order
+    // j = 0, 1, ... (dfft_exec_spectral_sum): a divergence, a component of a curl.  setOption("spectral_inputs", K) with K >= nin next to
+    // "spectral_op", before initFFT; table operators (kinds 1 .. 5) only, `out` differs from every input.
+    void execSpectralSum(void *out, const void *const *ins, const dfft_spectral_op *ops, int nin)
+    {
+        if (plan_) check(dfft_exec_spectral_sum(plan_, out, nin, ins, ops));
+    }
     // extension (no counterpart in the reference): buffers on the physical backing this plan's passes run fastest on, see
     // dfft_tune_placement in dfft_c.h; free them with dfft_free.  Collective on a multi-rank plan.
     void tunePlacement(const void *in, int tries, void **out, void **back = nullptr)

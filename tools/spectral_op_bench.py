@@ -13,7 +13,13 @@ yardstick for the ratios: run it more than once (--label names the run in the ou
 
 --outputs K (2 .. 8) times something else: ONE execSpectralOps with K kind-5 operators (components of the gradient of a Poisson solution:
 factor table i * k_d over the sums -|k|^2) against K calls of execSpectralOp with the same operators, on the same plan and buffers, the
-two alternating in one process.  It prints both times, their ratio and the ratio the trip counts predict, (4 + 6 K) / (10 K)."""
+two alternating in one process.  It prints both times, their ratio and the ratio the trip counts predict, (4 + 6 K) / (10 K).
+
+--inputs K (2 .. 8): ONE execSpectralSum of K inputs (kind-3 operators, the factor table i * k_d: a divergence) against what a caller writes
+without it -- K calls of execSpectralOp into K temporaries and their pointwise sum (torch, on the plan's stream) -- on the same plan and
+buffers, alternating in one process.  Trips of a domain-sized buffer: 7 K + 3 against 10 K plus the caller's sum; the line prints both
+ways of counting that sum, as one trip (10 K + 1, the figure the documents quote: 24/31 at K = 3) and as its K reads and one write
+(11 K + 1: 24/34)."""
 import argparse
 import os
 import statistics
@@ -121,6 +127,54 @@ def measure_outputs(n, prec, layout, K, reps, warmup):
     return {p: (statistics.median(v), min(v), max(v)) for p, v in times.items()}
 
 
+def measure_inputs(n, prec, layout, K, reps, warmup):
+    """(sum, singles): median, min, max in ms of one execSpectralSum with K inputs and of K execSpectralOp calls plus the pointwise sum"""
+    cdt, rdt = (torch.complex128, torch.float64) if prec == "double" else (torch.complex64, torch.float32)
+    esz = 16 if prec == "double" else 8
+    pl = dfft.MPIcuFFT_Pencil_Opt1(dfft.Configurations(), None, precision=prec)
+    pl.setOption("spectral_op", 1 if n & (n - 1) == 0 else 2)
+    pl.setOption("spectral_inputs", K)
+    pl.setOption("spectral_layout", layout)
+    pl.initFFT(dfft.GlobalSize(n, n, n), dfft.Pencil_Partition(1, 1), True)
+    stream = torch.cuda.current_stream()
+    pl.setStream(stream.cuda_stream)
+    nreal = n * n * n
+    bufs = [dfft.DeviceBuffer.alloc(nreal * esz // 2) for _ in range(2 * K + 1)]
+    us, tmps, out = [b.tensor(rdt) for b in bufs[:K]], [b.tensor(rdt) for b in bufs[K:2 * K]], bufs[2 * K].tensor(rdt)
+    g = torch.Generator(device="cuda").manual_seed(7)
+    for u in us:
+        u.copy_(torch.rand(nreal, generator=g, device="cuda", dtype=rdt) * 255 - 127.5)
+    ks = [torch.from_numpy(k).cuda() for k in pl.wavenumbers()]
+    ops = []
+    for j in range(K):
+        factors = [None, None, None]
+        factors[j % 3] = (1j * ks[j % 3].to(rdt)).to(cdt)
+        ops.append(dict(factors=tuple(factors), scale=1.0 / nreal))
+
+    def singles():
+        for t, u, op in zip(tmps, us, ops):
+            pl.execSpectralOp(t, u, **op)
+        torch.add(tmps[0], tmps[1], out=out)
+        for t in tmps[2:]:
+            out.add_(t)
+
+    paths = {"sum": lambda: pl.execSpectralSum(out, us, ops), "singles": singles}
+    times = {p: [] for p in paths}
+    for it in range(warmup + reps):
+        for name, fn in paths.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            fn()
+            b.record(stream)
+            b.synchronize()
+            if it >= warmup:
+                times[name].append(a.elapsed_time(b))
+    del us, tmps, out
+    for b in bufs:
+        b.free()
+    return {p: (statistics.median(v), min(v), max(v)) for p, v in times.items()}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", type=int, nargs="+", default=[512, 1024])
@@ -130,6 +184,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--outputs", type=int, default=0, metavar="K",
                     help="time one execSpectralOps with K operators against K calls of execSpectralOp instead of the paths (a) .. (d)")
+    ap.add_argument("--inputs", type=int, default=0, metavar="K",
+                    help="time one execSpectralSum of K inputs against K calls of execSpectralOp plus the pointwise sum instead of the paths (a) .. (d)")
     ap.add_argument("--label", default="")
     ap.add_argument("--out", default=None, help="append the result lines to this file")
     args = ap.parse_args()
@@ -137,6 +193,10 @@ def main():
         ap.error("--reps must be at least 20")
     if args.outputs and not 2 <= args.outputs <= 8:
         ap.error("--outputs must be 2 .. 8")
+    if args.inputs and not 2 <= args.inputs <= 8:
+        ap.error("--inputs must be 2 .. 8")
+    if args.inputs and args.outputs:
+        ap.error("--inputs and --outputs are separate measurements")
     lines = []
     for n in args.sizes:
         for prec in args.precisions:
@@ -148,6 +208,17 @@ def main():
                             + "  ".join(f"{name} {t[p][0]:8.3f} ({t[p][1]:.3f} .. {t[p][2]:.3f})" for p, name in
                                         (("multi", "one execSpectralOps"), ("singles", f"{K} x execSpectralOp")))
                             + f"   multi/singles = {t['multi'][0] / t['singles'][0]:.3f} (trips {4 + 6 * K}/{10 * K} = {(4 + 6 * K) / (10 * K):.3f})")
+                    print(line, flush=True)
+                    lines.append(line)
+                    continue
+                if args.inputs:
+                    K = args.inputs
+                    t = measure_inputs(n, prec, layout, K, args.reps, args.warmup)
+                    line = (f"{args.label + ' ' if args.label else ''}{n}^3 R2C {prec:<6s} spectral_layout={layout}  inputs={K}  reps={args.reps}  ms median (min .. max):  "
+                            + "  ".join(f"{name} {t[p][0]:8.3f} ({t[p][1]:.3f} .. {t[p][2]:.3f})" for p, name in
+                                        (("sum", "one execSpectralSum"), ("singles", f"{K} x execSpectralOp + sum")))
+                            + f"   sum/singles = {t['sum'][0] / t['singles'][0]:.3f} (trips {7 * K + 3}/{10 * K + 1} = {(7 * K + 3) / (10 * K + 1):.3f} "
+                              f"with the caller's sum as one trip, {7 * K + 3}/{11 * K + 1} = {(7 * K + 3) / (11 * K + 1):.3f} with its K + 1)")
                     print(line, flush=True)
                     lines.append(line)
                     continue
