@@ -5,6 +5,7 @@ import ctypes
 import os
 import re
 
+import numpy as np
 import pytest
 
 import distributedfft_amd as dfft
@@ -98,6 +99,62 @@ def test_axis_plans_cover_every_length_the_factors_allow():
             info = dfft.axis_plan_info(n, prec, two_level=1)
             assert info["kind"] == "two_level" and info["levels"][0][0] * info["levels"][1][0] == n
         assert dfft.axis_plan_info(127, prec, two_level=1)["kind"] == "bluestein" and dfft.axis_plan_info(2, prec, two_level=1)["kind"] == "native"
+
+
+def test_every_length_up_to_2_23_has_a_consistent_plan():
+    """README, DESIGN 3.2 and include/dfft_c.h: an axis plan for every length from 2 to 2^23.  Checked where the split rule changes its
+    mind -- within 64 of every power of two, the largest prime below each, 2000 seeded random lengths -- in both precisions: there is a
+    plan; its levels multiply to N (to the padded length M = next_pow2(2N - 1) <= 2^24 for long Bluestein); every level is within reach
+    of one launch of the generic kernel (a power of two up to 8192, or Bluestein over next_pow2(2F - 1) <= 8192 points).  Beyond 2^23
+    a length needs a split (8388609 = 3 x 2796203 has none), beyond 2^24 nothing has a plan.  No device is touched."""
+    def next_pow2(n):
+        return 1 << (n - 1).bit_length()
+
+    def is_prime(n):
+        return n >= 2 and all(n % d for d in range(2, int(n ** 0.5) + 1))
+
+    top = 1 << 23
+    lengths = set()
+    for e in range(2, 24):
+        lengths.update(n for n in range((1 << e) - 64, (1 << e) + 65) if 2 <= n <= top)
+        lengths.add(next(n for n in range((1 << e) - 1, 1, -1) if is_prime(n)))
+    rng = np.random.default_rng(20260223)
+    lengths.update(int(n) for n in rng.integers(2, top + 1, 2000))
+    assert {2, 3, 8191, 8388593, top - 64, top} <= lengths and len(lengths) > 4000
+    kinds = {"double": set(), "float": set()}
+    for prec in ("double", "float"):
+        for n in sorted(lengths):
+            info = dfft.axis_plan_info(n, prec)
+            assert info is not None, (n, prec)
+            kinds[prec].add(info["kind"])
+            if info["kind"] == "native":
+                assert info["M"] == n <= 8192 and info["levels"] == [], (n, info)
+                continue
+            if info["kind"] == "bluestein":
+                assert info["M"] == next_pow2(2 * n - 1) <= 8192 and info["levels"] == [], (n, info)
+                continue
+            whole = n
+            if info["kind"] == "long_bluestein":
+                whole = next_pow2(2 * n - 1)
+                assert info["M"] == whole <= 1 << 24, (n, info)
+            else:
+                assert info["kind"] == "two_level" and info["M"] == 0, (n, info)
+            (n1, m1, b1), (n2, m2, b2) = info["levels"]
+            assert n1 * n2 == whole, (n, info)
+            for f, m, blue in info["levels"]:
+                if blue:
+                    assert f >= 2 and m == next_pow2(2 * f - 1) <= 8192, (n, info)
+                else:
+                    assert f >= 2 and f & (f - 1) == 0 and m == f <= 8192, (n, info)
+        assert kinds[prec] == {"native", "bluestein", "two_level", "long_bluestein"}
+        # above 2^23 a length is too long to pad: it has a plan exactly if it splits into two factors within reach
+        for n in (8388609, (1 << 24) - 1, (1 << 24) + 1, (1 << 24) + 2, 1 << 25, 3 << 23):
+            info = dfft.axis_plan_info(n, prec)
+            splits = [d for d in range(2, int(n ** 0.5) + 1) if n % d == 0 and n <= 1 << 24
+                      and all(f & (f - 1) == 0 and f <= 8192 or 2 * f - 1 <= 8192 for f in (d, n // d))]
+            assert (info is not None) == bool(splits), (n, info)
+        assert dfft.axis_plan_info(8388609, prec) is None and dfft.axis_plan_info((1 << 24) + 1, prec) is None
+        assert dfft.axis_plan_info(1 << 24, prec)["levels"] == [(2048, 2048, False), (8192, 8192, False)]
 
 
 def test_in_register_butterflies_on_the_host(tmp_path):

@@ -170,6 +170,52 @@ def test_long_bluestein_lines(real, prec):
 
 
 # ------------------------------------------------------------------------------------------
+# a 2101248-point axis = Bluestein 513 x plain 4096: the shortest line with a plain sub-tile level (the workgroups of the 4096- and
+# 8192-point transforms take part of a tile's lines each), which every power of two from 2^23 on needs.  As the x axis of a C2C plan
+# (the pass's own strided address forms on the outer sides of the levels), as the real z axis (real_mode 1 and 2 of the two levels
+# with N / 2 + 1 spectral points) and under a 2 x 2 partition (segmented, chunked address forms on the outer sides).  The kernel-level
+# cases of the same form: test_gpu_two_level.py LONG_FORMS; on guarded buffers: test_gpu_footprint.py.
+# ------------------------------------------------------------------------------------------
+SUBTILE_AXIS = 2101248
+SUBTILE_LEVELS = [(513, 2048, True), (4096, 4096, False)]
+SUBTILE_SPECTRA = {}
+
+
+def subtile_axis_spectrum(g, shape, prec, real):
+    """the oracle's spectrum of two_level.single's centred input g (seed 5); the C2C ones are kept for test_gpu_footprint.py, which
+    runs the same shape (4 s of oracle each)"""
+    key = (tuple(shape), prec, real)
+    if key in SUBTILE_SPECTRA:
+        return SUBTILE_SPECTRA[key]
+    want = oracle_spectrum(g, prec, real)
+    if not real:
+        SUBTILE_SPECTRA[key] = want
+    return want
+
+
+def assert_subtile_axis(prec):
+    info = dfft.axis_plan_info(SUBTILE_AXIS, prec)
+    assert info is not None and info["kind"] == "two_level" and info["levels"] == SUBTILE_LEVELS, info
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("shape,real", [((SUBTILE_AXIS, 2, 3), False), ((2, 3, SUBTILE_AXIS), True)])
+def test_sub_tile_level_axis_single_rank(shape, real, prec):
+    assert_subtile_axis(prec)
+    g, got, back = two_level.single(shape, prec, not real, center=True)
+    want = subtile_axis_spectrum(g, shape, prec, real)
+    check_forward(got, want, prec, g.size, label=f"long line, sub-tile level: {shape} one rank {'R2C' if real else 'C2C'} centred")
+    assert rel(got, want) < TOL_FWD[prec]
+    round_trip_per_entry(back, g, g.size, prec, shape)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_sub_tile_level_axis_distributed(prec):
+    assert_subtile_axis(prec)
+    pencil_case("long line, sub-tile level", (SUBTILE_AXIS, 2, 4), 2, 2, prec, False)
+
+
+# ------------------------------------------------------------------------------------------
 # option single_order = 1: the single-rank pass order z, x, y
 # ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("prec", PRECS)

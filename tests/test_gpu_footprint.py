@@ -31,7 +31,8 @@ from oracle import oracle as orc  # noqa: E402
 
 import guarded  # noqa: E402
 from parity_metric import check_forward, check_forward_blocks, rms  # noqa: E402
-from test_gpu_entry_parity import PRECS, centred_input, is_pow2, kind, oracle_spectrum, round_trip_per_entry  # noqa: E402
+from test_gpu_entry_parity import (PRECS, assert_subtile_axis, centred_input, is_pow2, kind, oracle_spectrum,  # noqa: E402
+                                   round_trip_per_entry, subtile_axis_spectrum, SUBTILE_AXIS)
 from test_gpu_parity import mixed_lengths, run_distributed, run_distributed_real, run_partial, run_single  # noqa: E402
 from test_gpu_round3 import rmixed_lengths, run_single_order  # noqa: E402
 import test_gpu_slab_sequences as slabs  # noqa: E402
@@ -81,13 +82,13 @@ def pencil_case(family, shape, P1, P2, prec, real, options=None, chunks=None, of
     return plans
 
 
-def single_case(runner, what, real, **kw):
-    """the single-rank runners, runner(arena=arena, **kw): (input, spectrum, round trip)"""
+def single_case(runner, what, real, spectrum=oracle_spectrum, **kw):
+    """the single-rank runners, runner(arena=arena, **kw): (input, spectrum, round trip); spectrum(g, prec, real): the oracle's"""
     prec = kw["prec"]
     (g, got, back), (_, got0, back0) = both_fills(lambda arena: runner(arena=arena, **kw))
     written_and_same([got], [got0], what + " spectrum")
     written_and_same([back], [back0], what + " round trip")
-    check_forward(got, oracle_spectrum(g, prec, real), prec, g.size)
+    check_forward(got, spectrum(g, prec, real), prec, g.size)
     round_trip_per_entry(back, g, g.size, prec, what)
 
 
@@ -222,6 +223,16 @@ def test_long_lines(shape, real, axis, prec):
 def test_long_bluestein_lines(real, prec):
     assert kind(4099, prec) == "long_bluestein"
     pencil_case("long Bluestein", (6, 8, 4099), 2, 3, prec, real)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_long_line_with_a_sub_tile_level_single_rank(prec):
+    """(2101248, 2, 3): the scratch between the levels of a 2e6-point line (Bluestein 513 x plain 4096, sub-tile workgroups) within a
+    caller-owned work area of exactly getWorkSizeDevice() bytes"""
+    shape = (SUBTILE_AXIS, 2, 3)
+    assert_subtile_axis(prec)
+    single_case(two_level.single, f"long line, sub-tile level: {shape} one rank C2C {prec}", False,
+                spectrum=lambda g, p, real: subtile_axis_spectrum(g, shape, p, real), shape=shape, prec=prec, c2c=True, center=True)
 
 
 # ------------------------------------------------------------------------------------------

@@ -3,13 +3,19 @@ axis_plan_two_level): the lengths that have no kernel of their own -- beyond 819
 which the reference takes through cuFFT (mpicufft_pencil_opt1.cpp:165-197: cufftMakePlanMany64 accepts any size).
 
 * kernel level: natural lines, both directions, both precisions, forced on short lengths (variant -2: every pairing of
-  plain and Bluestein levels) and by itself on long ones;
+  plain and Bluestein levels) and by itself on long ones; at the end of the file the forms of a level that only lines beyond
+  131072 points have (plain levels of 1024 ... 8192 points, long Bluestein over 2^20 ... 2^24 padded points) up to the top of
+  the documented range, 2^24 points, against numpy in long double;
 * plans: long axes in every position, C2C and R2C (the real modes of the two levels), on one rank and distributed;
 * option two_level = 1 forces the two-level form on small grids for every pipeline (pencil, slab, the two slab
   sequences, chunked exchanges, partial transforms), compared with the oracle and with the one-launch kernels.
 
 Tolerances as in test_gpu_parity.py (fp64 1e-11 forward / 1e-10 round trip, fp32 1e-4 / 5e-5), relaxed by sqrt-ish growth on
 the lines of 10^4 .. 10^5 points where stated."""
+import functools
+import os
+import time
+
 import numpy as np
 import pytest
 
@@ -56,7 +62,8 @@ def fft1d_case(N, prec, variant, batch, big_prime=False, label=None):
 @pytest.mark.parametrize("N", FORCED)
 def test_fft1d_two_level_forced_vs_oracle(N, prec):
     """variant -2: two levels wherever the length splits -- plain x plain (64, 1024), plain x Bluestein (6, 3000),
-    Bluestein x Bluestein (15, 121, 1155), sub-tile inner transforms (8192 = 4096 x 2 is avoided by the cost model, 6144 not)"""
+    Bluestein x Bluestein (15, 121, 1155).  No sub-tile level here: the cost model avoids 8192 = 4096 x 2, and 6144 runs
+    48 x 128; the sub-tile workgroups of a 4096- or 8192-point level are held by the lengths of LONG_FORMS below"""
     fft1d_case(N, prec, -2, 45 if N < 4096 else 19, label="forced two-level" if N == FORCED[-1] else None)
 
 
@@ -300,3 +307,187 @@ def test_work_area_holds_the_level_scratch():
     want = orc.fft3d_c2c(g, -1)
     assert rel(d_out.cpu().numpy().reshape(shape), want) < 4e-11
     check_forward(d_out.cpu().numpy().reshape(shape), want, "double", g.size, zero_mean=False)
+
+
+# ------------------------------------------------------------------------------------------
+# Lines up to 2^24 points: the documented range (README, DESIGN 3.2, include/dfft_c.h) beyond LONG and LONG_BLUESTEIN above, whose
+# largest plain level is 512 points.  One length per form of a level that those never reach -- plain levels of 1024 and 2048 points,
+# the sub-tile workgroups of a plain 4096- or 8192-point level (Cfg::kSUB > 1 with PassArgs::plain), long Bluestein over M >= 2^20
+# padded points -- each at the smallest length that has it, and the top of the range.  Every case first asserts its plan, so that a
+# change of the cost model fails the test and does not move it to another form.
+#
+# fft1d_case's scheme (both directions, the reference's distribution and the same centred, the per-entry bound with factor 1, the old
+# bound beside it, the input bit-identical afterwards) with two differences the sizes ask for: the reference is numpy's transform in
+# long double (np.clongdouble: complex256 out), rounded once to complex128 -- 1e-16 of an entry, against bounds of 1e-12 -- and it is computed
+# once per input: the unnormalised inverse of x is the forward transform read backwards, ifft(x)[k] * N = fft(x)[(N - k) % N].
+# profiles/long_lines_parity_table.txt: the measured values and wall times (DFFT_PARITY_TABLE); profiles/long_lines_mutation.txt: the
+# fp64 cases on a library whose tables are rounded through fp32.
+# ------------------------------------------------------------------------------------------
+TILE_LINES = {"double": 8, "float": 16}      # getTileLines() of any plan (csrc/dfft_internal.hpp)
+
+
+def two(n1, m1, b1, n2, m2, b2):
+    return ("two_level", 0, [(n1, m1, bool(b1)), (n2, m2, bool(b2))])
+
+
+def longb(n1, n2):
+    return ("long_bluestein", n1 * n2, [(n1, n1, False), (n2, n2, False)])
+
+
+# (length, plan in both precisions); a level (F, M, bluestein): plain when M == F
+LONG_FORMS = [
+    pytest.param(132096, two(129, 512, 1, 1024, 1024, 0), id="132096-bluestein129xplain1024"),
+    pytest.param(524288, two(512, 512, 0, 1024, 1024, 0), id="524288-plain512xplain1024"),
+    pytest.param(526336, two(257, 1024, 1, 2048, 2048, 0), id="526336-bluestein257xplain2048"),
+    pytest.param(1048576, two(1024, 1024, 0, 1024, 1024, 0), id="1048576-plain1024xplain1024"),
+    pytest.param(4194304, two(2048, 2048, 0, 2048, 2048, 0), id="4194304-plain2048xplain2048"),
+    pytest.param(2101248, two(513, 2048, 1, 4096, 4096, 0), id="2101248-bluestein513xsubtile4096"),
+    pytest.param(4202496, two(513, 2048, 1, 8192, 8192, 0), id="4202496-bluestein513xsubtile8192"),
+    pytest.param(8388608, two(2048, 2048, 0, 4096, 4096, 0), id="8388608-plain2048xsubtile4096"),
+    pytest.param(262147, longb(1024, 1024), id="262147-long-bluestein-M1048576"),
+    pytest.param(1000003, longb(1024, 2048), id="1000003-long-bluestein-M2097152"),
+    # 2^21 + 1 = 3 x 699051 does not split: the smallest length above 2^21 that axis_plan_info reports as long Bluestein.  30 s a case,
+    # 22 s of it the host's long-double transform of the 2^23 chirp entries at the first call (axis_upload), 7 s the reference: slow
+    pytest.param(2097153, longb(2048, 4096), id="2097153-long-bluestein-M8388608", marks=pytest.mark.slow),
+]
+# the top of the range: the longest line, the longest with one / with two Bluestein levels of 4093 points (the largest prime whose
+# padded length fits one launch), the longest long-Bluestein line.  Centred input only.  2^24 takes 7 s a case (4 s of it the host's
+# table of 2^24 long-double twiddles) and stays in the default run; the two lengths with a factor of 4093 take 7 ... 12 s with their
+# composed reference and 8388593 takes 49 s (47 s of it the host's long-double transform of 2^24 chirp entries): slow
+# (profiles/long_lines_parity_table.txt)
+LONG_TOP = [
+    pytest.param(1 << 24, two(2048, 2048, 0, 8192, 8192, 0), id="16777216-plain2048xsubtile8192"),
+    pytest.param(16764928, two(4093, 8192, 1, 4096, 4096, 0), id="16764928-bluestein4093xsubtile4096", marks=pytest.mark.slow),
+    pytest.param(16752649, two(4093, 8192, 1, 4093, 8192, 1), id="16752649-bluestein4093xbluestein4093", marks=pytest.mark.slow),
+    pytest.param(8388593, longb(2048, 8192), id="8388593-long-bluestein-M16777216", marks=pytest.mark.slow),
+]
+
+
+def table_note(text):
+    path = os.environ.get("DFFT_PARITY_TABLE")
+    if path:
+        with open(path, "a") as f:
+            f.write(text + "\n")
+
+
+def largest_prime_factor(n):
+    p, f = 1, 2
+    while f * f <= n:
+        while n % f == 0:
+            p, n = f, n // f
+        f += 1
+    return max(p, n) if n > 1 else p
+
+
+@functools.lru_cache(maxsize=1)
+def composed_twiddles(n1, n2):
+    """exp(-2 pi i k1 m / (n1 n2)) for k1 < n1, m < n2, evaluated in long double"""
+    ang = -2 * np.longdouble("3.141592653589793238462643383279502884") / np.longdouble(n1 * n2) \
+        * (np.arange(n1, dtype=np.longdouble)[:, None] * np.arange(n2, dtype=np.longdouble)[None, :])
+    return (np.cos(ang) + 1j * np.sin(ang)).astype(np.complex128)
+
+
+def composed_fft(x, n1, n2):
+    """the transform of lines of n1 * n2 points composed from pocketfft's transforms of n1 and of n2 points (a prime factor of 4093
+    points goes through its Bluestein path there) and long-double twiddles between them: pocketfft takes 16764928 = 4093 x 4096 and
+    16752649 = 4093^2 points as a whole with an O(4093 N) pass, 38 s and 77 s a line; per entry the two differ by 8e-15 at both"""
+    b = x.shape[0]
+    a = np.fft.fft(x.reshape(b, n1, n2), axis=1)      # [k1][m], point n = n1-index * n2 + m
+    a *= composed_twiddles(n1, n2)[None]
+    a = np.fft.fft(a, axis=2)                         # [k1][k2] is output k1 + n1 * k2
+    return np.ascontiguousarray(a.transpose(0, 2, 1)).reshape(b, n1 * n2)
+
+
+def long_line_case(N, prec, plan, batch, inputs=(False, True), long_double=True, label="long line"):
+    """inputs: centred or not, in turn.  long_double=False: complex128 pocketfft as the reference (the top of the range: its own
+    per-entry error on the centred input is 1.5e-15 at 2^24 and 2.7e-15 at 8388593 against the long-double transform, a
+    thousandth of the fp64 bound), composed from its transforms of the two factors where it is slow as a whole (composed_fft).  The oracle's own transform is cross-checked against the reference where it is fast: up to
+    2^20 points without a large prime factor (it takes a prime length as an O(N^2) sum)."""
+    info = dfft.axis_plan_info(N, prec)
+    assert info is not None and (info["kind"], info["M"], info["levels"]) == plan, (N, prec, info)
+    if plan[0] == "long_bluestein":
+        assert plan[1] == 1 << (2 * N - 2).bit_length() and plan[1] >= 2 * N - 1
+    assert batch % TILE_LINES[prec] != 0, "a ragged number of lines, not a multiple of the tile"
+    t_case = time.time()
+    rng = np.random.default_rng(N)
+    x0 = rng.uniform(0, 255, (batch, N)) + 1j * rng.uniform(0, 255, (batch, N))
+    grow = max(1.0, np.log2(N) / 12.0)
+    with_oracle = N <= 1 << 20 and largest_prime_factor(N) <= 257
+    t_ref = t_first = t_gpu = 0.0
+    d_in = d_out = None
+    try:
+        for centred in inputs:
+            x = (x0 - CENTER * (1 + 1j) if centred else x0).astype(NPDT[prec])
+            t0 = time.time()
+            if long_double:
+                forward = np.fft.fft(x.astype(np.clongdouble), axis=-1)
+                assert forward.dtype == np.clongdouble
+                forward = forward.astype(np.complex128)
+            elif N > 1 << 20 and 2048 < largest_prime_factor(N) < N:
+                forward = composed_fft(x.astype(np.complex128), plan[2][0][0], plan[2][1][0])
+            else:
+                forward = np.fft.fft(x.astype(np.complex128), axis=-1)
+            t_ref += time.time() - t0
+            if with_oracle:
+                assert rel(orc.fft1d(x.astype(np.complex128), dfft.FORWARD), forward) < 1e-12
+            d_in = torch.from_numpy(x).cuda()
+            d_out = torch.zeros_like(d_in)
+            for direction in (dfft.FORWARD, dfft.INVERSE):
+                torch.cuda.synchronize()
+                t0 = time.time()
+                dfft.fft1d_batched(d_out, d_in, N, batch, direction, prec)
+                torch.cuda.synchronize()
+                if t_first == 0.0:
+                    t_first = time.time() - t0      # with the host's long-double table build (axis_upload)
+                else:
+                    t_gpu += time.time() - t0
+                got = d_out.cpu().numpy()
+                want = forward if direction == dfft.FORWARD else np.roll(forward[:, ::-1], 1, axis=-1)
+                check_forward(got, want, prec, N, zero_mean=centred, label=f"{label} fft1d N={N} x{batch} dir={direction} centred={centred}")
+                assert rel(got, want) < (2e-11 if prec == "double" else 2e-4) * grow
+                del got, want
+            assert np.array_equal(d_in.cpu().numpy(), x), "the pass must not modify its input"
+    finally:
+        del d_in, d_out
+        torch.cuda.empty_cache()
+    table_note(f"{label} fft1d N={N} x{batch} {prec}: wall {time.time() - t_case:.1f} s (reference {t_ref:.1f} s, first call with the table "
+               f"build {t_first:.2f} s, the other {2 * len(inputs) - 1} calls {t_gpu:.3f} s)")
+
+
+@pytest.mark.parametrize("prec", ["double", "float"])
+@pytest.mark.parametrize("N,plan", LONG_FORMS)
+def test_fft1d_long_line_forms_vs_long_double(N, plan, prec):
+    """every form of a level between the suite's 131072 points and the top of the range, 3 lines (2 above 5e6 points)"""
+    long_line_case(N, prec, plan, 3 if N < 5000000 else 2)
+
+
+@pytest.mark.parametrize("prec", ["double", "float"])
+def test_fft1d_long_line_on_more_than_one_tile(prec):
+    """TL + 1 lines of 524288 points: a second tile of lines (their own N points each in the scratch); centred input"""
+    long_line_case(524288, prec, two(512, 512, 0, 1024, 1024, 0), TILE_LINES[prec] + 1, inputs=(True,), label="long line, two tiles")
+
+
+@pytest.mark.parametrize("prec", ["double", "float"])
+@pytest.mark.parametrize("N,plan", LONG_TOP)
+def test_fft1d_top_of_the_range_vs_pocketfft(N, plan, prec):
+    """2 lines each of the longest lengths with a plan: tables of 2^24 entries, 32-bit point indices at their limit"""
+    long_line_case(N, prec, plan, 2, inputs=(True,), long_double=False, label="top of the range")
+
+
+@pytest.mark.parametrize("prec", ["double", "float"])
+@pytest.mark.parametrize("N", [(1 << 24) + 1, 8388609])
+def test_fft1d_beyond_the_range_is_refused(N, prec):
+    """2^24 + 1 is beyond the kernel's point indices, 8388609 = 3 x 2796203 neither splits nor pads within 2^24: ERR_UNSUPPORTED
+    before anything is launched (the buffers are whole lines all the same)"""
+    assert dfft.axis_plan_info(N, prec) is None
+    d_in = torch.zeros(N, dtype=torch.complex128 if prec == "double" else torch.complex64, device="cuda")
+    d_out = torch.full_like(d_in, 7.0)
+    try:
+        for direction in (dfft.FORWARD, dfft.INVERSE):
+            with pytest.raises(dfft.DfftError, match="error 4.*unsupported line length"):
+                dfft.fft1d_batched(d_out, d_in, N, 1, direction, prec)
+        torch.cuda.synchronize()
+        assert bool((d_out == 7.0).all()) and not bool(d_in.any()), "a refused call must not touch its buffers"
+    finally:
+        del d_in, d_out
+        torch.cuda.empty_cache()
